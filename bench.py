@@ -17,7 +17,13 @@ regenerates all N x M random features; Z is never written), the RCCL all-reduce 
 preconditioner apply and the float64 vector updates, including the per-iteration convergence
 check.  value = N * M * K / t  random features per second (whole job); cg_iters_per_sec = K / t.
 
-Besides the contract fields the JSON line carries
+A plain run sets up (data, one preconditioner build), warms up, times the K steps and prints the headline fields
+(metric, value, unit, n_gpus, steps, warmup, ms_per_step, cg_iters_per_sec, higher_is_better, dtype, config, final_loss
+and its check against the stored value).  --dump-outputs DIR writes what the timed solve returned after its last step:
+DIR/weights.npy (the CG iterate, float64) and DIR/losses.npy (the per-iteration residuals, float64).  The inputs are
+seeded, so two builds can be compared output for output.
+
+With --full the JSON line also carries
   roofline      -- the dominant kernel (ztz3_kernel, the fused matvec): algorithmic HBM bytes (4*d per row)
                    over its measured duration (HIP events on the launch stream)
   featgen_op    -- the stand-alone cudaRBFFeatureGen-equivalent operator (Z materialised as
@@ -86,6 +92,12 @@ def parse():
     ap.add_argument("--dim", type=int, default=1024)
     ap.add_argument("--rffs", type=int, default=8192)
     ap.add_argument("--rank-precond", type=int, default=512)
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: rooflines, time to tolerance, cached mode, the other configs, the CPU "
+                         "baseline, per-rank and all-reduce figures (--cpu-seconds, --no-cpu-baseline, --no-configs and "
+                         "--no-direct-child apply to this mode)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the timed solve's outputs after its last step as DIR/<name>.npy")
     ap.add_argument("--cpu-seconds", type=float, default=12.0,
                     help="CPU-baseline budget: whole 8192-row chunks are processed until this much time is spent")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -125,7 +137,7 @@ def direct_rccl_child(args, limit_s=None, cmd=None, side_file=None):
     """First contact of the opt-in on-stream all-reduce (XGPR_RCCL_DIRECT=1: ``xgpr_allreduce_sum_f64`` on a communicator
     created through the C ABI, xgpr_amd/dist.py) with more than one GPU, without putting the driver's number at risk:
     AFTER rank 0 has printed the job's JSON line and the process group is gone, rank 0 starts a FRESH job -- a child
-    ``python bench.py --gpus N --steps 20 --no-configs --no-cpu-baseline`` in a session of its own, which starts its own N
+    ``python bench.py --gpus N --steps 20 --full --no-configs --no-cpu-baseline`` in a session of its own, which starts its own N
     ranks (self_launch; never an exec of this process, which has touched the GPU) -- under a wall-clock watchdog.  What the
     child's line says about the direct path (``direct_equals_torch_allreduce``, ``final_loss_check``, the all-reduce time
     per iteration, ms per step) goes to stderr and to a side file.  Nothing here can change this process's exit code or
@@ -139,7 +151,7 @@ def direct_rccl_child(args, limit_s=None, cmd=None, side_file=None):
         if cmd is None:
             cmd = [sys.executable, os.path.abspath(__file__), "--gpus", str(args.gpus), "--steps", "20", "--warmup", str(args.warmup),
                    "--rows", str(args.rows), "--dim", str(args.dim), "--rffs", str(args.rffs), "--rank-precond",
-                   str(args.rank_precond), "--no-configs", "--no-cpu-baseline", "--no-direct-child"]
+                   str(args.rank_precond), "--full", "--no-configs", "--no-cpu-baseline", "--no-direct-child"]
         env = {k: v for k, v in os.environ.items() if k not in TORCHRUN_ENV}
         env["XGPR_RCCL_DIRECT"] = "1"
         env["XGPR_BENCH_CHILD"] = "1"
@@ -687,6 +699,21 @@ def valu_only_probe(kern, ds, kern_ms, device):
     return {"ms": ms, "frac": ms / kern_ms, "source": "live: libxgpr_hip_valuonly_probe.so (timing-only build, -DXGPR_ABL_VALUONLY)"}
 
 
+def close(comm):
+    import torch
+    torch.cuda.synchronize()
+    comm.close()                   # the direct RCCL communicator (if any): every rank is here, its stream is idle
+    if comm.through_backend:
+        torch.distributed.destroy_process_group()
+
+
+def exit_on_loss_mismatch(loss_check, loss):
+    """Called after the line is printed: a final loss other than the stored one makes the run exit non-zero."""
+    if loss_check["ok"] is False:
+        raise SystemExit(f"final loss {loss!r} differs from the stored {loss_check['expected']!r} (rtol {loss_check['rtol']}): "
+                         "the timed iterations did not do the work they claim")
+
+
 def main():
     args = parse()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and "RANK" not in os.environ:
@@ -717,7 +744,7 @@ def main():
     if comm.world_size != args.gpus:
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={comm.world_size}")
     device = torch.device("cuda", torch.cuda.current_device())
-    dist_info = dist_summary(comm, device, args.rffs)
+    dist_info = dist_summary(comm, device, args.rffs) if args.full else None
     from xgpr_amd.kernels import make_kernel
     from xgpr_amd.dataset import DeviceDataset, build_regression_dataset
     from xgpr_amd.preconditioner import RandNysPreconditioner
@@ -734,21 +761,22 @@ def main():
     # rank-512 SRHT preconditioner from ALL rows (one pass: HIP feature-gen + HIP SRHT per 8192-row
     # chunk, float64 MFMA GEMM for acc += SRHT(Z)^T Z; ~0.3 s at N = 1e6) -- outside the timed region
     ds_pre = DeviceDataset(x, y, None, 8192, ds.get_ymean(), ds.get_ystd(), n, device, comm)
-    # one small untimed build first: the first GEMM / eigensolver / Cholesky calls of a process pay ~0.4 s of
-    # library initialisation that is not part of a build
-    warm_rows = min(hi - lo, 16384)
-    RandNysPreconditioner(kern, DeviceDataset(x[:warm_rows], y[:warm_rows], None, 8192, ds.get_ymean(), ds.get_ystd(),
-                                               warm_rows * comm.world_size, device, comm),
-                          args.rank_precond, False, 123, "srht")
-    comm.barrier()
-    torch.cuda.synchronize()
-    tp0 = time.perf_counter()
-    pre = RandNysPreconditioner(kern, ds_pre, args.rank_precond, False, 123, "srht")
-    torch.cuda.synchronize()
-    precond_first_s = time.perf_counter() - tp0
-    # built twice: the first full-size build also pays for the allocator's first 4 GiB window / 0.5 GiB sketch blocks
-    # (hipMalloc: 0 ... 0.3 s depending on the box); the second is the build itself.  Both are reported.
-    del pre
+    if args.full:
+        # one small untimed build first: the first GEMM / eigensolver / Cholesky calls of a process pay ~0.4 s of
+        # library initialisation that is not part of a build
+        warm_rows = min(hi - lo, 16384)
+        RandNysPreconditioner(kern, DeviceDataset(x[:warm_rows], y[:warm_rows], None, 8192, ds.get_ymean(), ds.get_ystd(),
+                                                   warm_rows * comm.world_size, device, comm),
+                              args.rank_precond, False, 123, "srht")
+        comm.barrier()
+        torch.cuda.synchronize()
+        tp0 = time.perf_counter()
+        pre = RandNysPreconditioner(kern, ds_pre, args.rank_precond, False, 123, "srht")
+        torch.cuda.synchronize()
+        precond_first_s = time.perf_counter() - tp0
+        # built twice: the first full-size build also pays for the allocator's first 4 GiB window / 0.5 GiB sketch blocks
+        # (hipMalloc: 0 ... 0.3 s depending on the box); the second is the build itself.  Both are reported.
+        del pre
     comm.barrier()
     torch.cuda.synchronize()
     tp0 = time.perf_counter()
@@ -769,7 +797,6 @@ def main():
         orig(xs, vec, out, ws, **kw)
         e1.record()
         timings.append((e0, e1))
-    kern.ztz_matvec = timed_matvec
 
     # the exchange step of the iteration: torch.distributed's all-reduce of w.  ProcessGroupNCCL runs RCCL on its
     # own stream and chains it to the compute stream with events on both sides; the pair of events recorded here on
@@ -786,7 +813,9 @@ def main():
         e1.record()
         ar_timings.append((e0, e1))
         return tensor
-    comm.all_reduce_ = timed_all_reduce
+    if args.full:
+        kern.ztz_matvec = timed_matvec
+        comm.all_reduce_ = timed_all_reduce
 
     def run(iters):
         resid = torch.zeros((m, 2, 1), dtype=torch.float64, device=device)
@@ -800,7 +829,7 @@ def main():
     comm.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    _, _, niter, losses = run(args.steps)
+    weights, _, niter, losses = run(args.steps)
     torch.cuda.synchronize()
     comm.barrier()
     t1 = time.perf_counter()
@@ -812,6 +841,38 @@ def main():
     if comm.through_backend:
         torch.distributed.all_reduce(elapsed, op=torch.distributed.ReduceOp.MAX)
     t = float(elapsed.item())
+    if args.dump_outputs and comm.rank == 0:
+        # what a caller of the timed solve receives (the iterate is replicated over the ranks): small, written whole
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "weights.npy"), weights.cpu().numpy().astype(np.float64))
+        np.save(os.path.join(args.dump_outputs, "losses.npy"), np.asarray(losses, dtype=np.float64))
+    from xgpr_amd import _lib as xlib
+    build_id = xlib.build_id()     # sha256 of csrc/*, include/xgpr_hip.h and the compiler flags the LOADED library was built from
+    line = {
+        "metric": "random-features/sec (fused CG matvec; every CG iteration regenerates all N x M features)",
+        "value": n * m * args.steps / t,
+        "unit": "random-features/s",
+        "n_gpus": args.gpus, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": 1e3 * t / args.steps,
+        "cg_iters_per_sec": args.steps / t,
+        "higher_is_better": True,
+        "scaling": "strong",
+        "vs_baseline": None,
+        "dtype": "f32 (SORF + cos/sin) / f64 (Z^T Z p accumulation and CG state)",
+        "data": "synthetic",
+        "build_id": build_id,
+        "config": {"workload": "BASELINE configs[2]: Matern-5/2, N=%d, d=%d, %d RFFs, rows sharded over %d GPU(s), "
+                               "rank-%d SRHT preconditioner (all rows), CG step" %
+                               (n, d, m, args.gpus, args.rank_precond),
+                   "rows_per_gpu": hi - lo, "lambda": 0.1, "sigma": 1.0},
+        "final_loss": losses[-1], "final_loss_check": loss_check,
+    }
+    if not args.full:
+        if comm.rank == 0:
+            print(json.dumps(line))
+        close(comm)
+        exit_on_loss_mismatch(loss_check, losses[-1])
+        return
     kern_ms = float(np.mean([a.elapsed_time(b) for a, b in timings]))
     ar_ms = float(np.mean([a.elapsed_time(b) for a, b in ar_timings])) if ar_timings else 0.0
     kern.ztz_matvec = orig
@@ -996,8 +1057,6 @@ def main():
         # rocprofv3 --pmc passes of this same command, corrected as MI355X_MICROARCH.md prescribes;
         # profiles/r2_pmc_traffic.json), not a quantity of this run -- quoted only for the configuration it was
         # measured on, and labelled as such in the line
-        from xgpr_amd import _lib as xlib
-        build_id = xlib.build_id()     # sha256 of csrc/*, include/xgpr_hip.h and the compiler flags the LOADED library was built from
         traffic = None
         pm, traffic_src = stored_profile("pmc_traffic.json", build_id)
         try:
@@ -1041,28 +1100,13 @@ def main():
         fg_bytes = (4.0 * d + 8.0 * m) * fg_rows
         fg_gbs = fg_bytes / (fg_ms * 1e-3) / 1e9
         out = {
-            "metric": "random-features/sec (fused CG matvec; every CG iteration regenerates all N x M features)",
-            "value": n * m * args.steps / t,
-            "unit": "random-features/s",
-            "n_gpus": args.gpus, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": 1e3 * t / args.steps,
-            "cg_iters_per_sec": args.steps / t,
-            "higher_is_better": True,
-            "scaling": "strong",
-            "vs_baseline": None,
-            "dtype": "f32 (SORF + cos/sin) / f64 (Z^T Z p accumulation and CG state)",
-            "data": "synthetic",
-            "build_id": build_id,
+            **line,
             "direct_rccl_child": (None if args.gpus == 1 else
                                   "after this line rank 0 starts a fresh `bench.py --gpus %d` with XGPR_RCCL_DIRECT=1 under a watchdog; its record "
                                   "(direct_equals_torch_allreduce, final_loss_check, all-reduce times) goes to stderr and "
                                   "gpurun_out/bench_direct_rccl_child.json and cannot change this line or the exit code" % args.gpus
                                   if (not args.no_direct_child and "XGPR_BENCH_CHILD" not in os.environ
                                       and os.environ.get("XGPR_BENCH_DIRECT_CHILD", "1") != "0") else "off"),
-            "config": {"workload": "BASELINE configs[2]: Matern-5/2, N=%d, d=%d, %d RFFs, rows sharded over %d GPU(s), "
-                                   "rank-%d SRHT preconditioner (all rows), CG step" %
-                                   (n, d, m, args.gpus, args.rank_precond),
-                       "rows_per_gpu": n_local, "lambda": 0.1, "sigma": 1.0},
             "roofline": {"kernel": "ztz3_kernel<10> (+ pack_radem, reduce_slabs)", "bound": "hbm",
                          "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
                          "traffic": traffic, "traffic_source": (traffic_src + " (rocprofv3 --pmc passes of this command on this build; "
@@ -1082,7 +1126,6 @@ def main():
                                           "allreduce_ms_per_iter": v[2], "rows": int(v[3])} for i, v in enumerate(per_rank)],
                             "allreduce_note": "allreduce_ms_per_iter is measured by HIP events on the compute stream around the "
                                               "all-reduce of w (allreduce_path), inside the timed CG iterations"},
-            "final_loss": losses[-1], "final_loss_check": loss_check,
             "fit_to_tol": fit_to_tol,
             "configs": configs,
             "precond_build": {"seconds": precond_build_s, "first_build_seconds": precond_first_s, "rows": n,
@@ -1103,10 +1146,7 @@ def main():
         else:
             out["cpu_baseline"] = None
         print(json.dumps(out))
-    torch.cuda.synchronize()
-    comm.close()                   # the direct RCCL communicator (if any): every rank is here, its stream is idle
-    if comm.through_backend:
-        torch.distributed.destroy_process_group()
+    close(comm)
     if (args.gpus > 1 and comm.rank == 0 and not args.no_direct_child and "XGPR_BENCH_CHILD" not in os.environ
             and os.environ.get("XGPR_BENCH_DIRECT_CHILD", "1") != "0"):
         sys.stdout.flush()
@@ -1117,9 +1157,7 @@ def main():
         else:
             time.sleep(float(os.environ.get("XGPR_BENCH_CHILD_DELAY", "3")))
             direct_rccl_child(args)    # never raises, never touches stdout or the exit code
-    if loss_check["ok"] is False:
-        raise SystemExit(f"final loss {losses[-1]!r} differs from the stored {loss_check['expected']!r} (rtol {loss_check['rtol']}): "
-                         "the timed iterations did not do the work they claim")
+    exit_on_loss_mismatch(loss_check, losses[-1])
 
 
 if __name__ == "__main__":

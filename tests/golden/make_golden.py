@@ -58,10 +58,46 @@ def import_reference():
     return xGPR
 
 
+PART_BYTES = 900 * 1024      # every committed file stays under 1 MiB
+
+
 def save(name, **arrays):
+    """One .npz, or -- when it would pass PART_BYTES -- parts name, name.part2.npz, ... each under it; an array too large
+    for one part is stored as row blocks key@0, key@1, ...  tests/conftest.py load_golden puts them back together."""
+    import io
+    import zipfile
     path = os.path.join(HERE, name)
-    np.savez_compressed(path, **arrays)
-    print(f"wrote {name}: {os.path.getsize(path) / 1024:.0f} KiB")
+    for old in [path] + [os.path.join(HERE, f) for f in os.listdir(HERE) if f.startswith(name[:-4] + ".part")]:
+        if os.path.exists(old):
+            os.remove(old)
+
+    def packed_size(arrs):
+        buf = io.BytesIO()
+        np.savez_compressed(buf, **arrs)
+        return buf.tell()
+    sized = []
+    for k, a in arrays.items():
+        a = np.asarray(a)
+        size = packed_size({k: a})
+        nblk = -(-size // PART_BYTES)
+        if nblk > 1:
+            for i, blk in enumerate(np.array_split(a, nblk)):
+                sized.append((f"{k}@{i}", blk, packed_size({k: blk})))
+        else:
+            sized.append((k, a, size))
+    parts, cur, cur_size = [], {}, 0
+    for k, a, size in sized:
+        if cur and cur_size + size > PART_BYTES:
+            parts.append(cur)
+            cur, cur_size = {}, 0
+        cur[k] = a
+        cur_size += size
+    parts.append(cur)
+    for i, part in enumerate(parts):
+        p = path if i == 0 else os.path.join(HERE, f"{name[:-4]}.part{i + 1}.npz")
+        np.savez_compressed(p, **part)
+        assert zipfile.is_zipfile(p) and os.path.getsize(p) < 1024 * 1024, p
+        print(f"wrote {os.path.basename(p)}: {os.path.getsize(p) / 1024:.0f} KiB")
 
 
 # ---------------------------------------------------------------- G1: bare FHT
@@ -692,9 +728,22 @@ def g18_cfg5_precond(xgpr):
     save("g18_cfg5_precond.npz", **out)
 
 
+def ref_core_digests():
+    """ref_core_digests.json: sha256 of every output of tests/test_oracle_vs_ref.py's seeded cases, computed by the
+    reference core (the oracle must reproduce them bit for bit where the core cannot be built)."""
+    import json
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import test_oracle_vs_ref as t
+    out = {key: {name: t.digest(a) for name, a in outputs_of(REF).items()} for key, outputs_of in t.all_cases()}
+    with open(os.path.join(HERE, "ref_core_digests.json"), "w") as f:
+        json.dump(out, f, indent=1, sort_keys=True)
+        f.write("\n")
+    print(f"wrote ref_core_digests.json: {len(out)} cases")
+
+
 if __name__ == "__main__":
     # python make_golden.py            -> everything;   python make_golden.py g17 g18  -> only the named fixtures
-    plain = [g1_fht, g2_rbf, g3_conv, g4_maxpool, g5_srht]
+    plain = [g1_fht, g2_rbf, g3_conv, g4_maxpool, g5_srht, ref_core_digests]
     with_ref = [g6_draws, g7_cg, g8_e2e, g9_exact, g10_nmll, g11_classifier, g12_mini_ard, g13_rank_selection,
                 g14_two_layer, g15_crude_tuning, g16_aux, g17_cfg4_conv, g18_cfg5_precond]
     wanted = set(sys.argv[1:])

@@ -50,7 +50,7 @@ def test_whole_bench_through_the_backend_with_one_rank():
     env.update({"XGPR_DIST_FORCE": "1", "HSA_ENABLE_IPC_MODE_LEGACY": env.get("HSA_ENABLE_IPC_MODE_LEGACY", "0")})
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", "29549", os.path.join(ROOT, "bench.py"), "--gpus", "1", "--rows", "40000", "--steps", "4",
-           "--warmup", "1", "--no-cpu-baseline"]
+           "--warmup", "1", "--full", "--no-cpu-baseline"]
     res = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-2000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
@@ -69,7 +69,7 @@ def _two_gloo_ranks(extra_env, tmp_path):
     env.update({"XGPR_DIST_BACKEND": "gloo", "XGPR_LOCAL_DEVICE": "0", "XGPR_BENCH_CHILD_FILE": str(tmp_path / "child.json")})
     env.update(extra_env)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--rows", "31250", "--steps", "3", "--warmup", "1",
-           "--no-cpu-baseline", "--no-configs"]
+           "--full", "--no-cpu-baseline", "--no-configs"]
     res = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
     return res, lines

@@ -5,7 +5,7 @@ GRBM_GUI_ACTIVE is summed over the 8 XCDs (MI355X_MICROARCH.md): clock = counter
 that clock is 1024 SIMDs x 32 flop/cycle (one v_mfma_f64_16x16x4_f64 = 2048 flop per 64 cycles)."""
 import csv, glob, json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-G = os.path.join(ROOT, "gpurun_out")
+G = os.environ.get("XGPR_PROF_OUT", os.path.join(ROOT, "prof_out"))
 out = {}
 # issued flop per launch: the contraction 2 * rows * M * rank; a block kernel 2 * rows * M * (16 + 12) columns at k = 26
 SPEC = {"sketch_gemm_lds_kernel": ("prof_mfma_gemm", 2.0 * 131072 * 8192 * 512, 2.0 * 131072 * 8192 * 512),

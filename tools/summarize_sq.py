@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
-"""profiles/r1_fused_pmc_sq.json from the two SQ passes of tools/collect_profiles.sh (gpurun_out/prof_sq1, prof_sq2:
+"""profiles/r1_fused_pmc_sq.json from the two SQ passes of tools/collect_profiles.sh (prof_sq1, prof_sq2 under $XGPR_PROF_OUT:
 rocprofv3 --pmc ... -- python tools/pmc_probe.py, the fused CG matvec at cfg3 shape on 262144 rows).  gfx950: SQ_*
 cycle counters are in units of 4 cycles, GRBM_GUI_ACTIVE is summed over the 8 XCDs (MI355X_MICROARCH.md)."""
 import csv, glob, json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-G, P = os.path.join(ROOT, "gpurun_out"), os.path.join(ROOT, "profiles")
+G, P = os.environ.get("XGPR_PROF_OUT", os.path.join(ROOT, "prof_out")), os.path.join(ROOT, "profiles")
 ROWS, TILES_PER_ROW, SIMDS, CUS = 262144, 4, 1024, 256
 # second argument: substring of the kernel name to summarise (default: the fused matvec); third: wave tiles of the launch
 KSEL = sys.argv[2] if len(sys.argv) > 2 else "ztz3_kernel"
