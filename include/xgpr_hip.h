@@ -268,7 +268,10 @@ int xgpr_precond_apply_f64(const double *u, const double *inv_eig, double prefac
  * xgpr_rbf_feature_cache_f32 is cudaRBFFeatureGen (xgpr_cuda_rfgen_cpp_ext.cpp:32-40) writing the
  * float32 (cos, sin) pairs *before* scaling into zc[n, num_rffs] -- exactly the values whose
  * widening times the scale is the float64 output -- so a shard's Z stays in HBM (32 KB per
- * datapoint at 8192 features).  xgpr_zcache_matvec_f32 is then the chunk body of the CG matvec
+ * datapoint at 8192 features).  Every padded width: up to 4096 on the three-wave kernel's feature mode, 8192 on
+ * wave tiles, wider on the any-width path (padded rows beyond 32768 floats transform in the workspace's global scratch:
+ * pass xgpr_sorf_workspace_bytes(radem_shape2, d, 4) of workspace; xgpr_rbf_workspace_bytes suffices up to 32768).
+ * xgpr_zcache_matvec_f32 is then the chunk body of the CG matvec
  * (fitting_toolkit/cg_tools.py:189-191) streamed from that cache at HBM speed:
  * w_out = sum_i z_i (z_i . v), z_i = scale * zc[i] with Z[:,0] = 1 under fit_intercept; float64
  * accumulation, deterministic.  num_freqs <= 16384 (one tile of 1024 frequencies per wave up to 8192,
@@ -283,6 +286,13 @@ int xgpr_zcache_matvec_f32(const float *zc, const double *v, double *w_out, long
  * already set): w_out = scale^2 * sum_i c_i (c_i . v). */
 int xgpr_zcache_matvec_scaled_f32(const float *zc, const double *v, double *w_out, long n, long num_rffs,
                                   double scale, void *workspace, size_t workspace_bytes, void *stream);
+/* z^T y from the same float32 rows (exact_nmll_calcs.py:35-37 without float64 Z): out[m] = sum_i z_i[m] y_i,
+ * z_i = scale * zc[i] with z_i[0] = 1 when fit_intercept; scale <= 0 selects the RBF-family constant of
+ * xgpr_rbf_feature_cache_f32, a positive scale is for caches that hold complete feature rows / scale.  y float64 [n],
+ * out float64 [num_rffs] (overwritten); float64 accumulation, partial sums over row ranges added in a fixed order
+ * (deterministic).  zc, y and out 8-byte aligned; workspace as for xgpr_zcache_matvec_f32. */
+int xgpr_zcache_zty_f32(const float *zc, const double *y, double *out, long n, long num_rffs, int fit_intercept,
+                        double scale, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---- SRHTCompressor.transform_x in one pass (srht_compressor.py:87-97: zero-pad the chunk to the padded
  * width, cudaSRHT in place, gather the sampled columns): out[i, c] = SRHT(z_i)[sampler[c]] for c < ncols,

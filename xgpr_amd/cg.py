@@ -21,6 +21,41 @@ import torch
 from .dist import SINGLE
 
 
+def rows_ok(kernel):
+    """Whether the kernel's float32 feature rows can be regenerated (SORFKernel.rows_ok); kernels without that method
+    answer with fused_ok."""
+    return getattr(kernel, "rows_ok", kernel.fused_ok)()
+
+
+def rows_matvec_ok(kernel):
+    """Whether the k = 1 matvec can be applied from this kernel's float32 rows (resident or regenerated): rows_ok, and
+    the streaming kernel (num_freqs <= 16384) or the block contractions (num_rffs % 4 == 0) -- the cache_ok condition."""
+    return rows_ok(kernel) and hasattr(kernel, "cache_ok") and kernel.cache_ok()
+
+
+def holds_cache(dataset, kernel):
+    """Whether the dataset already holds the resident feature cache of ``kernel`` at its current sigma."""
+    return (getattr(dataset, "_zcache_key", None) == (id(kernel), float(kernel.hyperparams[1]))
+            and getattr(dataset, "_zcache", None) is not None)
+
+
+def row_windows(xs, kernel, holder, window_bytes):
+    """(first row, float32 feature rows) over the scaled shard ``xs``, regenerated window by window into one scratch
+    buffer of at most ~``window_bytes`` (kept on ``holder._zwin`` when a holder is given: repeated passes reuse it)."""
+    n, m = xs.shape[0], kernel.get_num_rffs()
+    win = max(1024, min(n, window_bytes // (4 * m)))
+    zwin = getattr(holder, "_zwin", None)
+    if zwin is None or zwin.shape != (win, m) or zwin.device != xs.device:
+        zwin = torch.empty((win, m), dtype=torch.float32, device=xs.device)
+        if holder is not None:
+            holder._zwin = zwin
+    for lo in range(0, n, win):
+        hi = min(n, lo + win)
+        zc = zwin[:hi - lo]
+        kernel.fill_feature_cache(xs[lo:hi], zc)
+        yield lo, zc
+
+
 def calc_zty(dataset, kernel):
     """exact_nmll_calcs.py:13-39 -> (z^T y [M] f64 device, y^T y float), summed over ranks."""
     comm = dataset.comm
@@ -30,6 +65,22 @@ def calc_zty(dataset, kernel):
         y = dataset.normalized_y()
         kernel.zty(dataset.scaled_x(kernel.hyperparams[1]), y, z_trans_y)
         y_trans_y = (y ** 2).sum().reshape(1)
+    elif rows_ok(kernel) and torch.device(kernel.device).type == "cuda":
+        # no fused kernel at this width: z^T y from float32 rows -- the resident cache when the dataset holds one,
+        # otherwise windows regenerated into scratch
+        y = dataset.normalized_y()
+        y_trans_y = (y ** 2).sum().reshape(1)
+        ws = torch.empty(kernel.workspace_bytes(), dtype=torch.uint8, device=kernel.device)
+        if holds_cache(dataset, kernel):
+            zc = dataset.feature_cache(kernel)
+            if zc.shape[0] > 0:
+                kernel.zty_cached(zc, y, z_trans_y, ws)
+        else:
+            part = torch.empty_like(z_trans_y)
+            xs = dataset.scaled_x(kernel.hyperparams[1])
+            for lo, zc in row_windows(xs, kernel, None, ConjugateGrad.BLOCK_WINDOW_BYTES):
+                kernel.zty_cached(zc, y[lo:lo + zc.shape[0]], part, ws)
+                z_trans_y += part
     else:
         y_trans_y = torch.zeros(1, dtype=torch.float64, device=kernel.device)
         for xin, yin, ldata in dataset.get_chunked_data():
@@ -86,6 +137,12 @@ class ConjugateGrad:
                 self._ws = torch.empty(kernel.workspace_bytes(), dtype=torch.uint8, device=xs.device)
                 self._ws_masks_of = None
             self._matvec_cols(kernel, xs, vec, matvec)
+        elif vec.shape[1] <= 2 and vec.is_cuda and rows_matvec_ok(kernel):
+            # no fused kernel at this width: one column at a time over float32 rows (resident or regenerated)
+            tmp = torch.empty(vec.shape[0], dtype=torch.float64, device=vec.device)
+            for j in range(vec.shape[1]):
+                self._ztz_rows(dataset, kernel, vec[:, j].contiguous(), tmp)
+                matvec[:, j] = tmp
         elif self.BLOCK_KERNELS and vec.is_cuda and hasattr(kernel, "block_ok") and kernel.block_ok():
             self._matvec_block(dataset, kernel, vec, matvec)
         else:
@@ -116,19 +173,12 @@ class ConjugateGrad:
         if self.cache_features and dataset.get_local_ndatapoints() > 0:
             zc = dataset.feature_cache(kernel)
             kernel.ztz_block_cached(zc, vec, out, self._block_ws(zc.shape[0], kernel, k, vec.device))
-        elif kernel.fused_ok():
+        elif rows_ok(kernel):
             xs = dataset.scaled_x(kernel.hyperparams[1])
-            n = xs.shape[0]
-            win = max(1024, min(n, self.BLOCK_WINDOW_BYTES // (4 * m)))
-            if self._zwin is None or self._zwin.shape != (win, m) or self._zwin.device != vec.device:
-                self._zwin = torch.empty((win, m), dtype=torch.float32, device=vec.device)
-            for lo in range(0, n, win):
-                hi = min(n, lo + win)
-                zc = self._zwin[:hi - lo]
-                kernel.fill_feature_cache(xs[lo:hi], zc)
+            for _lo, zc in row_windows(xs, kernel, self, self.BLOCK_WINDOW_BYTES):
                 # (per window: a SHORTER last window can need a larger workspace -- the split projection's partials are reserved
                 # for short launches only; _block_ws only grows)
-                kernel.ztz_block_cached(zc, vec, out, self._block_ws(hi - lo, kernel, k, vec.device), accumulate=True)
+                kernel.ztz_block_cached(zc, vec, out, self._block_ws(zc.shape[0], kernel, k, vec.device), accumulate=True)
         else:
             for x, lengths in dataset.get_chunked_x_data():
                 zc = kernel.transform_x(x, lengths).to(torch.float32)
@@ -143,6 +193,28 @@ class ConjugateGrad:
             kernel.ztz_matvec(xs, vec[:, j].contiguous(), tmp, self._ws)
             matvec[:, j] = tmp
 
+    def _ztz_rows(self, dataset, kernel, vec, out):
+        """out <- Z^T (Z vec) of this rank's rows for one right-hand side from float32 feature rows, where no fused kernel
+        serves the width: the resident cache, or windows regenerated into scratch (hipZCacheMatvec per window)."""
+        if self._ws is None or self._ws.numel() < kernel.workspace_bytes() or self._ws.device != out.device:
+            self._ws = torch.empty(kernel.workspace_bytes(), dtype=torch.uint8, device=out.device)
+            self._ws_masks_of = None
+        if dataset.get_local_ndatapoints() == 0:
+            out.zero_()
+        elif self._use_cache(kernel):
+            kernel.ztz_matvec_cached(dataset.feature_cache(kernel), vec, out, self._ws)
+        else:
+            xs = dataset.scaled_x(kernel.hyperparams[1])
+            part = None
+            for lo, zc in row_windows(xs, kernel, self, self.BLOCK_WINDOW_BYTES):
+                if lo == 0:
+                    kernel.ztz_matvec_cached(zc, vec, out, self._ws)
+                    continue
+                if part is None:
+                    part = torch.empty_like(out)
+                kernel.ztz_matvec_cached(zc, vec, part, self._ws)
+                out += part
+
     def _ztz(self, dataset, kernel, vec, out):
         """out <- sum over ranks of Z^T (Z vec) for one right-hand side (fused kernel +
         all-reduce); lambda^2 vec is added by the caller."""
@@ -151,6 +223,8 @@ class ConjugateGrad:
             self._ws_masks_of = None
         if self._use_cache(kernel):
             kernel.ztz_matvec_cached(dataset.feature_cache(kernel), vec, out, self._ws)
+        elif not kernel.fused_ok() and rows_matvec_ok(kernel):
+            self._ztz_rows(dataset, kernel, vec, out)
         else:
             # the Rademacher sign masks are packed into the workspace by the first call only
             radem = getattr(kernel, "radem_diag", None)
@@ -419,7 +493,7 @@ class ConjugateGrad:
         or (x_k, alphas, betas) with ``nmll_settings``."""
         dev = resid.device
         if (resid.shape[2] == 1 and not nmll_settings and dev.type == "cuda"
-                and (kernel.fused_ok() or self._use_cache(kernel))
+                and (kernel.fused_ok() or rows_matvec_ok(kernel) or self._use_cache(kernel))
                 and (preconditioner is None or hasattr(preconditioner, "u_mat"))):
             return self._fit_one_rhs_device(dataset, kernel, preconditioner, resid, maxiter, tol, verbose, trace)
         if (self.BLOCK_DEVICE_SOLVE and 1 < resid.shape[2] <= 32 and dev.type == "cuda" and trace is None

@@ -19,7 +19,7 @@ from dataclasses import dataclass
 import torch
 
 from . import xgpr_hip_rfgen_ext as ext
-from .cg import _resolve_cache_mode
+from .cg import _resolve_cache_mode, row_windows, rows_ok
 from .kernels import block_workspace_bytes
 
 
@@ -63,17 +63,9 @@ class NonlinearCGClassification:
         if self.cache_features:
             yield ds.feature_cache(kernel), labels
             return
-        if kernel.fused_ok():
-            xs = ds.scaled_x(kernel.hyperparams[1])
-            n, m = xs.shape[0], kernel.get_num_rffs()
-            win = max(1024, min(n, self.WINDOW_BYTES // (4 * m)))
-            if self._zwin is None or self._zwin.shape != (win, m):
-                self._zwin = torch.empty((win, m), dtype=torch.float32, device=xs.device)
-            for lo in range(0, n, win):
-                hi = min(n, lo + win)
-                zc = self._zwin[:hi - lo]
-                kernel.fill_feature_cache(xs[lo:hi], zc)
-                yield zc, labels[lo:hi]
+        if rows_ok(kernel):
+            for lo, zc in row_windows(ds.scaled_x(kernel.hyperparams[1]), kernel, self, self.WINDOW_BYTES):
+                yield zc, labels[lo:lo + zc.shape[0]]
             return
         row = 0
         for x, lengths in ds.get_chunked_x_data():

@@ -117,7 +117,9 @@ __global__ void global_stage_kernel(T *x, long npairs, long h) {
     x[j + h] = a - b;
 }
 
-enum { MODE_RBF = 0, MODE_RBF_GRAD = 1, MODE_CONV = 2, MODE_CONV_GRAD = 3, MODE_MAXPOOL = 4 };
+// MODE_RBF_CACHE: the float32 feature cache rows (xgpr_rbf_feature_cache_f32) -- (cos, sin) before scaling, the values MODE_RBF
+// widens and multiplies by its constant (T = float only)
+enum { MODE_RBF = 0, MODE_RBF_GRAD = 1, MODE_CONV = 2, MODE_CONV_GRAD = 3, MODE_MAXPOOL = 4, MODE_RBF_CACHE = 5 };
 
 template <typename T> struct SorfArgs {
     const T *x; double *out; double *grad; float *outf;
@@ -170,7 +172,11 @@ __global__ void generic_sorf_kernel(SorfArgs<T> a) {
         }
         for (int e = tid; e < cnt; e += nt) {
             const T chv = a.chi[out0 + e];
-            if (MODE == MODE_RBF || MODE == MODE_CONV) {
+            if (MODE == MODE_RBF_CACHE) {
+                T sn, cs;
+                Math<T>::sincos(buf[e] * chv, sn, cs);
+                *reinterpret_cast<float2 *>(a.outf + i * 2 * a.F + 2 * (long)(out0 + e)) = make_float2((float)cs, (float)sn);
+            } else if (MODE == MODE_RBF || MODE == MODE_CONV) {
                 T prod = buf[e] * chv;
                 T sn, cs;
                 Math<T>::sincos(prod, sn, cs);

@@ -210,6 +210,12 @@ int launch_ztz3_feat(WaveArgs a, long P, int lg, hipStream_t st) {
     return 1;
 }
 
+// XGPR_F64_PLAN=generic in the environment: the shapes of wave_tile.inc run on the any-width path instead (A/B timing)
+bool wave_tile_plan_off() {
+    static const bool off = [] { const char *e = getenv("XGPR_F64_PLAN"); return e && e[0] == 'g'; }();
+    return off;
+}
+
 template <typename T>
 int rbf_impl(const T *x, double *out, double *grad, const int8_t *radem, const T *chi, long n, long d,
              long out_rows, long num_rffs, long grad_rows, long grad_cols, long num_freqs, long R,
@@ -285,7 +291,7 @@ int rbf_impl(const T *x, double *out, double *grad, const int8_t *radem, const T
         // wave tiles in registers + an LDS image (wave_tile.inc): the float64 feature and gradient operators at P <= 8192, the float32
         // gradient operator at 2048 <= P <= 8192 and the float32 feature operator at P = 8192 (narrower ones are served above);
         // XGPR_F64_PLAN=generic keeps the any-width path (A/B)
-        static const bool generic64 = [] { const char *e = getenv("XGPR_F64_PLAN"); return e && e[0] == 'g'; }();
+        const bool generic64 = wave_tile_plan_off();
         const bool mine = sizeof(T) == 8 ? P <= 8192 : (((want_grad && P > 1024) || P > 4096) && P <= 8192);
         if (mine && !generic64 && R % 64 == 0 && (reinterpret_cast<uintptr_t>(radem) & 15) == 0) {
             // rbf_ops.cpp:180-185: a double constant in the gradient op
@@ -389,7 +395,7 @@ int conv_impl(const T *x, double *out, double *grad, float *outf, const int8_t *
     {
         // wave tiles in registers + an LDS image (wave_tile.inc): float64 input at every padded window width up to 4096, float32 input at
         // 2048 / 4096 (narrower float32 windows were served above); XGPR_F64_PLAN=generic keeps the any-width path (A/B)
-        static const bool generic64 = [] { const char *e = getenv("XGPR_F64_PLAN"); return e && e[0] == 'g'; }();
+        const bool generic64 = wave_tile_plan_off();
         const bool mine = sizeof(T) == 8 ? P <= 4096 : (P > 1024 && P <= 4096);      // (8 / 16 waves per transform leave too few registers for the accumulators)
         const bool aligned = mode == MODE_MAXPOOL || (aligned16(out) && (mode != MODE_CONV_GRAD || aligned16(grad)));
         if (mine && !generic64 && aligned && R % 64 == 0 && (reinterpret_cast<uintptr_t>(radem) & 15) == 0) {
@@ -641,10 +647,25 @@ int zcache_build_impl(const float *x, float *zc, const int8_t *radem, const floa
     if (num_rffs < 2 || (num_rffs & 1) != 0) return fail(XGPR_ERR_ODD_OUTPUT, "last dim of output must be even number");
     if (2 * num_freqs != num_rffs || num_freqs > R) return fail(XGPR_ERR_RFFS_FREQS, "incorrect number of rffs and or freqs.");
     if (R % P != 0) return fail(XGPR_ERR_RFFS_FREQS, "incorrect number of rffs and or freqs.");
-    if (P > 4096) return fail(XGPR_ERR_UNSUPPORTED, "the feature cache supports padded width <= 4096");
     if (!workspace || wbytes < masks_bytes(R)) return fail(XGPR_ERR_WORKSPACE, "workspace too small (see xgpr_rbf_workspace_bytes)");
     if ((reinterpret_cast<uintptr_t>(zc) & 7) != 0) return fail(XGPR_ERR_WORKSPACE, "cache pointer must be 8-byte aligned");
     hipStream_t st = (hipStream_t)stream;
+    if (P > 4096) {
+        // the transforms of the float32 feature operator at the same width (rbf_impl): wave tiles at P = 8192 under that operator's own
+        // conditions, the any-width path otherwise (in LDS up to 32768 floats, beyond that in the workspace's global scratch:
+        // xgpr_sorf_workspace_bytes)
+        if (d > 2147483647L) return fail(XGPR_ERR_UNSUPPORTED, "the feature cache: input width beyond 2^31 - 1");
+        SorfArgs<float> s = {};
+        s.x = x; s.outf = zc; s.radem = radem; s.chi = chi;
+        s.n = n; s.row_stride = d; s.F = num_freqs; s.R = R; s.d = (int)d;
+        s.P = (int)P; s.reps = (int)((num_freqs + P - 1) / P); s.nc = norm_constant<float>(P);
+        if (P == 8192 && !wave_tile_plan_off() && R % 64 == 0 && (reinterpret_cast<uintptr_t>(radem) & 15) == 0) {
+            using WT = WaveTile<float, 13>;
+            return launch_wave_tile(wave_tile_rbf_cache_kernel<13>, s, n * (R / 1024), WT::WAVES, WT::LDS_BYTES, st,
+                                    "wave_tile_rbf_cache_kernel launch");
+        }
+        return launch_generic_sorf<float, MODE_RBF_CACHE>(s, workspace, wbytes, st);
+    }
     WaveArgs a = {};
     a.x = x; a.outf = zc; a.masks = (const uint64_t *)workspace; a.chi = chi;
     a.n = n; a.row_stride = d; a.F = num_freqs; a.d = (int)d;
@@ -731,6 +752,36 @@ int zcache_matvec_impl(const float *zc, const double *vec, double *w_out, long n
     HIP_TRY(hipGetLastError(), "zcache_ztz_kernel launch");
     hipLaunchKernelGGL(reduce_slabs_kernel, dim3((unsigned)((num_rffs + 63) / 64)), dim3(256), 0, st, a.wpart, w_out,
                        num_rffs, nblocks * a.G);
+    HIP_TRY(hipGetLastError(), "reduce_slabs_kernel launch");
+    return 0;
+}
+
+// z^T y over float32 feature rows (xgpr_zcache_zty_f32): ~8 workgroups per CU of 512 columns x a contiguous range of rows, partial
+// sums in slabs of the workspace (the matvec's ZTZ_MAX_SLABS x M doubles), added in slab order -- the geometry depends on n, M and the
+// device only, so the result is reproducible bit for bit
+int zcache_zty_impl(const float *zc, const double *y, double *out, long n, long num_rffs, int fit_intercept, double scale_override,
+                    void *workspace, size_t wbytes, void *stream) {
+    if (n == 0) return fail(XGPR_ERR_NO_DATAPOINTS, "no datapoints");
+    if (num_rffs < 2 || (num_rffs & 1) != 0) return fail(XGPR_ERR_ODD_OUTPUT, "last dim of output must be even number");
+    if (((reinterpret_cast<uintptr_t>(zc) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(out)) & 7) != 0)
+        return fail(XGPR_ERR_WORKSPACE, "cache, y and output pointers must be 8-byte aligned");
+    const size_t need = (size_t)ZTZ_MAX_SLABS * num_rffs * sizeof(double);
+    if (!workspace || wbytes < need || !aligned16(workspace))
+        return fail(XGPR_ERR_WORKSPACE, "workspace too small (see xgpr_ztz_matvec_workspace_bytes)");
+    hipStream_t st = (hipStream_t)stream;
+    const long F = num_rffs / 2;
+    const double scale = scale_override > 0.0 ? scale_override : rbf_scale<float>(F, fit_intercept);
+    const long ncb = (num_rffs + 511) / 512;
+    long nslabs = (8 * device_cus() + ncb - 1) / ncb;
+    if (nslabs > ZTZ_MAX_SLABS) nslabs = ZTZ_MAX_SLABS;
+    if (nslabs > n) nslabs = n;
+    const long rows_per_slab = (n + nslabs - 1) / nslabs;
+    nslabs = (n + rows_per_slab - 1) / rows_per_slab;
+    double *wpart = reinterpret_cast<double *>(workspace);
+    hipLaunchKernelGGL(zcache_zty_kernel, dim3((unsigned)ncb, (unsigned)nslabs), dim3(256), 0, st, zc, y, wpart, n, num_rffs,
+                       rows_per_slab, fit_intercept, scale);
+    HIP_TRY(hipGetLastError(), "zcache_zty_kernel launch");
+    hipLaunchKernelGGL(reduce_slabs_kernel, dim3((unsigned)((num_rffs + 63) / 64)), dim3(256), 0, st, wpart, out, num_rffs, nslabs);
     HIP_TRY(hipGetLastError(), "reduce_slabs_kernel launch");
     return 0;
 }

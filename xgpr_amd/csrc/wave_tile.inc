@@ -207,6 +207,37 @@ template <typename T> __device__ __forceinline__ void elem_sincos(const T x, con
     } else Math<T>::sincos(x, sn, cs);
 }
 
+// The front of the fixed-vector operators on wave tiles, ONE copy for wave_tile_rbf_kernel and wave_tile_rbf_cache_kernel (the cache's
+// bit-for-bit contract with the feature operator rests on it): this wave's (datapoint i, tile b), the tile's SORF and the products
+// with chi -- on return v[r] = prodVal of frequency 1024 b + 64 r + lane (layout C; shared_rfgen_ops.cpp:107).  Returns false for a
+// wave past the last item: a narrow transform returns before any work, a wide one repeats a live item (the workgroup's barriers; the
+// caller stores nothing for it).
+template <typename T, int LOG2P>
+__device__ __forceinline__ bool wt_rbf_front(const SorfArgs<T> &a, T *tbuf, T (&v)[16], long &i, int &b) {
+    using WT = WaveTile<T, LOG2P>;
+    const int lane = threadIdx.x & 63;
+    const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    long item = wv + (long)blockIdx.x * WT::WAVES;
+    // wide transforms: every tile of the diagonal's length is computed (R is a multiple of P), the ones past F just store nothing
+    const int nb = WT::WIDE ? (int)(a.R >> 10) : (int)((a.F + 1023) >> 10);
+    const bool live = item < a.n * nb;
+    if constexpr (!WT::WIDE) { if (!live) return false; }
+    else if (!live) item -= 2;            // NW == 2, n * nb = 2 mod 4: the last workgroup's spare pair repeats the live pair (barriers; no stores)
+    i = item / nb;
+    b = __builtin_amdgcn_readfirstlane((int)(item % nb));
+    const WT wt(tbuf, wv, lane);
+    int4 rw[3];
+    wt.load(v, a.x + i * a.row_stride, a.d);
+    wt.load_signs(rw, a.radem, a.R, b);
+    wt.sorf(v, rw, a.nc);
+    #pragma unroll
+    for (int r = 0; r < 16; r++) {
+        const long f = (long)b * 1024 + 64 * r + lane;
+        v[r] *= a.chi[f < a.F ? f : 0];                       // prodVal = xdata[i] * chiIn[i] (shared_rfgen_ops.cpp:107)
+    }
+    return live;
+}
+
 // T = double: the float64 feature operator (GRAD false) and the float64 gradient operator (GRAD true: cudaRBFGrad, rbf_ops.cpp:112-189,
 // shared_rfgen_ops.cpp:140-155 with its roundings back to T).  T = float, GRAD true: the float32 gradient operator at padded widths
 // 2048 / 4096 (up to 1024 it runs on wave_rbf_kernel<LOG2P, OUT_GRAD>, the feature operator at every width on ztz3_kernel's feature modes).
@@ -217,28 +248,13 @@ __global__ __launch_bounds__(wt_waves(LOG2P) * 64) void wave_tile_rbf_kernel(Sor
     extern __shared__ __attribute__((aligned(16))) unsigned char wt_lds[];            // WT::LDS_BYTES (one image per wave)
     T *tbuf = reinterpret_cast<T *>(wt_lds);
     const int lane = threadIdx.x & 63;
-    const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    long item = wv + (long)blockIdx.x * WT::WAVES;
-    // wide transforms: every tile of the diagonal's length is computed (R is a multiple of P), the ones past F just store nothing
-    const int nb = WT::WIDE ? (int)(a.R >> 10) : (int)((a.F + 1023) >> 10);
-    bool live = item < a.n * nb;
-    if constexpr (!WT::WIDE) { if (!live) return; }
-    else if (!live) item -= 2;            // NW == 2, n * nb = 2 mod 4: the last workgroup's spare pair repeats the live pair (barriers; no stores)
-    const long i = item / nb;
-    const int b = __builtin_amdgcn_readfirstlane((int)(item % nb));
-    const WT wt(tbuf, wv, lane);
     T v[16];
-    int4 rw[3];
-    wt.load(v, a.x + i * a.row_stride, a.d);
-    wt.load_signs(rw, a.radem, a.R, b);
-    wt.sorf(v, rw, a.nc);
+    long i;
+    int b;
+    const bool live = wt_rbf_front<T, LOG2P>(a, tbuf, v, i, b);
+    if constexpr (!WT::WIDE) { if (!live) return; }
     // layout C: register r of lane l is frequency 1024 b + 64 r + l -- one store instruction writes 64 consecutive (cos, sin) pairs
     double *orow = a.out + i * 2 * a.F;
-    #pragma unroll
-    for (int r = 0; r < 16; r++) {
-        const long f = (long)b * 1024 + 64 * r + lane;
-        v[r] *= a.chi[f < a.F ? f : 0];                       // prodVal = xdata[i] * chiIn[i] (shared_rfgen_ops.cpp:107)
-    }
     if constexpr (GRAD) {
         // cudaRBFGrad (shared_rfgen_ops.cpp:140-155): the input is not pre-multiplied by sigma; every product is rounded back to T; the
         // scale is a double constant (rbf_ops.cpp:180-185)
@@ -269,6 +285,29 @@ __global__ __launch_bounds__(wt_waves(LOG2P) * 64) void wave_tile_rbf_kernel(Sor
             elem_sincos(v[r], big, sn, cs);
             if (f < a.F && live) *reinterpret_cast<double2 *>(orow + 2 * f) = make_double2(cs * a.scale, sn * a.scale);
         }
+    }
+}
+
+// The float32 feature cache rows (xgpr_rbf_feature_cache_f32) at P = 8192: the transform of wave_tile_rbf_kernel<float, 13, false>, the
+// (cos, sin) pairs stored as float32 BEFORE scaling -- the values that kernel widens and multiplies by its constant -- into outf[i, 2 f ..].
+template <int LOG2P>
+__global__ __launch_bounds__(wt_waves(LOG2P) * 64) void wave_tile_rbf_cache_kernel(SorfArgs<float> a) {
+    using WT = WaveTile<float, LOG2P>;
+    static_assert(WT::WIDE, "the cache rows up to P = 4096 run on ztz3_kernel's feature modes");
+    extern __shared__ __attribute__((aligned(16))) unsigned char wt_lds[];
+    float *tbuf = reinterpret_cast<float *>(wt_lds);
+    const int lane = threadIdx.x & 63;
+    float v[16];
+    long i;
+    int b;
+    const bool live = wt_rbf_front<float, LOG2P>(a, tbuf, v, i, b);
+    float *orow = a.outf + i * 2 * a.F;
+    #pragma unroll
+    for (int r = 0; r < 16; r++) {
+        const long f = (long)b * 1024 + 64 * r + lane;
+        float sn, cs;
+        elem_sincos(v[r], false, sn, cs);                     // (the feature mode's call for T = float)
+        if (f < a.F && live) *reinterpret_cast<float2 *>(orow + 2 * f) = make_float2(cs, sn);
     }
 }
 

@@ -391,6 +391,10 @@ int xgpr_zcache_matvec_scaled_f32(const float *zc, const double *v, double *w_ou
     if (!(scale > 0.0)) return fail(XGPR_ERR_ARRAY_DIMS, "scale must be positive");
     return zcache_matvec_impl(zc, v, w_out, n, num_rffs, 0, scale, workspace, workspace_bytes, stream);
 }
+int xgpr_zcache_zty_f32(const float *zc, const double *y, double *out, long n, long num_rffs, int fit_intercept, double scale,
+                        void *workspace, size_t workspace_bytes, void *stream) {
+    return zcache_zty_impl(zc, y, out, n, num_rffs, fit_intercept, scale, workspace, workspace_bytes, stream);
+}
 
 size_t xgpr_zcache_block_workspace_bytes(long n, long num_rffs, long k) {
     if (n <= 0 || num_rffs <= 0 || k < 1) return 0;

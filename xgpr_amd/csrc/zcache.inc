@@ -316,3 +316,37 @@ __global__ __launch_bounds__(256) void reduce_slabs_short_kernel(const double *_
     }
 }
 
+
+// ---- z^T y from float32 feature rows (the resident cache or a regenerated window): slab s of wpart [nslabs, M] receives
+// sum over rows [s * rows_per_slab, (s + 1) * rows_per_slab) of z_i[m] y_i, z_i = scale * zc[i] (z_i[0] = 1 under fit_intercept),
+// accumulated in float64 in row order; reduce_slabs_kernel then adds the slabs in a fixed order.  Workgroup (c, s): 512 columns, thread
+// t columns 512 c + 2 t and + 1 (one 8-byte load per row: M is even), four rows' loads issued before their arithmetic.
+__global__ __launch_bounds__(256) void zcache_zty_kernel(const float *__restrict__ zc, const double *__restrict__ y, double *wpart,
+                                                         long n, long M, long rows_per_slab, int fit_intercept, double scale) {
+    const long c = (long)blockIdx.x * 512 + 2 * threadIdx.x;
+    if (c >= M) return;
+    const long r0 = (long)blockIdx.y * rows_per_slab;
+    const long r1 = r0 + rows_per_slab < n ? r0 + rows_per_slab : n;
+    const bool icpt = fit_intercept && c == 0;
+    double a0 = 0.0, a1 = 0.0;
+    long r = r0;
+    for (; r + 4 <= r1; r += 4) {
+        float2 z[4];
+        double yv[4];
+        #pragma unroll
+        for (int q = 0; q < 4; q++) { z[q] = *reinterpret_cast<const float2 *>(zc + (r + q) * M + c); yv[q] = y[r + q]; }
+        #pragma unroll
+        for (int q = 0; q < 4; q++) {
+            const double ys = yv[q] * scale;
+            a0 = icpt ? a0 + yv[q] : __builtin_fma((double)z[q].x, ys, a0);
+            a1 = __builtin_fma((double)z[q].y, ys, a1);
+        }
+    }
+    for (; r < r1; r++) {
+        const float2 z = *reinterpret_cast<const float2 *>(zc + r * M + c);
+        const double ys = y[r] * scale;
+        a0 = icpt ? a0 + y[r] : __builtin_fma((double)z.x, ys, a0);
+        a1 = __builtin_fma((double)z.y, ys, a1);
+    }
+    *reinterpret_cast<double2 *>(wpart + (long)blockIdx.y * M + c) = make_double2(a0, a1);
+}

@@ -167,7 +167,7 @@ class SORFKernel(KernelBase):
         """k = 1 streaming kernel up to num_freqs = 16384 (a workgroup holds all tiles of a datapoint: one tile
         per wave up to 8192, two beyond); past that the resident cache is applied through the two block
         contractions with one column."""
-        return self.fused_ok() and (self.num_freqs <= 16384 or self.block_ok())
+        return self.rows_ok() and (self.num_freqs <= 16384 or self.block_ok())
 
     def cache_pays(self):
         """Whether streaming the resident cache beats regenerating the features in a k = 1 solve: the launcher's own
@@ -198,10 +198,22 @@ class SORFKernel(KernelBase):
     # ---- block of right-hand sides (approximate-NMLL probes, k = 26): float64 matrix cores over
     # the float32 cache, either the resident one or a window of rows regenerated into scratch
     def block_ok(self):
-        return padded_dims(self._xdim[-1]) <= FUSED_MAX_WIDTH and self.num_rffs % 4 == 0
+        """The block operators read float32 rows: regenerated ones wherever ``rows_ok`` (and, at padded width <= 4096 with
+        more than 65536 frequencies, float64 feature chunks rounded to float32); they need num_rffs % 4 == 0."""
+        return (self.rows_ok() or padded_dims(self._xdim[-1]) <= FUSED_MAX_WIDTH) and self.num_rffs % 4 == 0
 
     def fill_feature_cache(self, x_scaled, zcache):
         ext.hipRBFFeatureCache(x_scaled, zcache, self.radem_diag, self.chi_arr)
+
+    def rows_ok(self):
+        """Whether ``fill_feature_cache`` can write this kernel's float32 rows: wherever the fused kernels run (padded
+        width <= 4096), and at every wider padded width up to 65536 frequencies (wave tiles at 8192, the any-width
+        path beyond).  There the solver's passes read regenerated rows or the resident cache instead of float64 Z."""
+        return self.fused_ok() or (padded_dims(self._xdim[-1]) > FUSED_MAX_WIDTH and self.num_freqs <= 65536)
+
+    def zty_cached(self, zcache, y, out, workspace):
+        """out <- Z^T y from float32 rows of this kernel (the resident cache or a regenerated window)."""
+        ext.hipZCacheZtY(zcache, y, out, self.fit_intercept, workspace)
 
     def ztz_block_cached(self, zcache, vecs, out, workspace, accumulate=False):
         _block_matvec(zcache, vecs, out, workspace, self.fit_intercept, 0.0, accumulate)
@@ -231,7 +243,8 @@ class SORFKernel(KernelBase):
         return ext.ztz_workspace_bytes(self.num_rffs, self.radem_diag.shape[2])
 
 
-FUSED_MAX_WIDTH = 4096   # padded input width the wave-tile kernels serve (include/xgpr_hip.h); beyond it: the any-width LDS path
+FUSED_MAX_WIDTH = 4096   # padded input width of the fused regenerate-and-reduce kernels (fused_ok, include/xgpr_hip.h); beyond it
+                         # the fixed-vector kernels' solver passes run on float32 rows (rows_ok: regenerated windows or the cache)
 
 BLOCK_COLS = 32          # right-hand sides per call of the block matvec (include/xgpr_hip.h)
 

@@ -23,6 +23,7 @@ import numpy as np
 import torch
 
 from . import xgpr_hip_rfgen_ext as ext
+from .cg import rows_ok
 from .kernels import SRHTCompressor
 
 ROW_WINDOW_BYTES = 4 << 30        # float32 feature rows regenerated per window of the accumulation passes
@@ -32,7 +33,7 @@ def _rows_path_ok(dataset, kernel, rank, from_cache, need_bt=False):
     """Whether the accumulation passes can run on float32 feature rows (module docstring)."""
     if not hasattr(kernel, "row_cache_params") or torch.device(kernel.device).type != "cuda":
         return False
-    if not from_cache and not (hasattr(kernel, "fused_ok") and kernel.fused_ok() and hasattr(kernel, "fill_feature_cache")):
+    if not from_cache and not (hasattr(kernel, "fused_ok") and rows_ok(kernel) and hasattr(kernel, "fill_feature_cache")):
         return False
     m = kernel.get_num_rffs()
     if m % 2 != 0 or (need_bt and m % 4 != 0) or not hasattr(dataset, "scaled_x"):
@@ -401,7 +402,7 @@ class RandNysPreconditioner:
             raise RuntimeError("Unknown method supplied for tuning preconditioner construction.")
         if cache_features == "auto":
             from .cg import _resolve_cache_mode
-            from_cache = (hasattr(kernel, "fused_ok") and not kernel.fused_ok()
+            from_cache = (hasattr(kernel, "fused_ok") and not rows_ok(kernel)
                           and hasattr(kernel, "cache_rows_to_features")
                           and _resolve_cache_mode("auto", kernel, dataset, block=True))
         else:

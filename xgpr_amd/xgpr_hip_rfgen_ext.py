@@ -616,6 +616,22 @@ def hipZCacheMatvec(cacheArr, vec, outVec, fitIntercept, workspace):
         C.c_void_p(workspace.data_ptr()), C.c_size_t(workspace.numel()), _stream()))
 
 
+def hipZCacheZtY(cacheArr, yvec, outVec, fitIntercept, workspace, scale=0.0):
+    """``outVec = Z.T @ yvec`` from float32 feature rows (exact_nmll_calcs.py:35-37 without float64 Z): Z = scale *
+    cacheArr with Z[:, 0] = 1 under fitIntercept; scale = 0 selects the RBF-family scale, a positive scale is for caches
+    that already hold complete feature rows / scale.  ``workspace``: ztz_workspace_bytes of bytes, as hipZCacheMatvec."""
+    zc = _dev(cacheArr, "cacheArr", torch.float32, 2)
+    y = _dev(yvec, "yvec", torch.float64, 1)
+    o = _dev(outVec, "outVec", torch.float64, 1)
+    if yvec.shape[0] != cacheArr.shape[0]:
+        raise TypeError("yvec: one value per datapoint expected")
+    if outVec.shape[0] != cacheArr.shape[1]:
+        raise TypeError("outVec: expected num_rffs entries")
+    return _lib.check(_LIB.xgpr_zcache_zty_f32(
+        zc, y, o, cacheArr.shape[0], cacheArr.shape[1], int(bool(fitIntercept)), float(scale),
+        C.c_void_p(workspace.data_ptr()), C.c_size_t(workspace.numel()), _stream()))
+
+
 def hipZCacheBlockMatvec(cacheArr, vecs, outVecs, fitIntercept, workspace, scale=0.0, accumulate=False):
     """``outVecs (+)= Z.T @ (Z @ vecs)`` for vecs [num_rffs, k <= 32] on the float64 matrix cores, Z streamed
     from the resident feature cache (cg_tools.py:41-44 with a block of right-hand sides).  scale = 0 selects
