@@ -132,6 +132,29 @@ int xgpr_conv1d_fgen_f64(const double *x, double *out, const int8_t *radem, cons
                          long radem_shape2, long nseq, int conv_width, int scaling_type,
                          void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- float32 feature rows of the sequence kernels (Conv1d* / Graph* RBF, Matern, Cauchy).  Stands in for
+ * cudaConv1dFGen (xgpr_cuda_rfgen_cpp_ext.cpp:70-80) followed by the host code around it
+ * (kernel_baseclass.py:269-299: zeroed float64 output, `xtrans[:, 0] = 1` under an intercept) and a cast to float32:
+ * zc[n, num_rffs] (float32, row-major, 8-byte aligned) is OVERWRITTEN -- no zero fill needed -- with exactly the
+ * value xgpr_conv1d_fgen_f32 adds into a zeroed float64 output, rounded once to float32 (round to nearest even), and
+ * zc[:, 0] = 1.0f when fit_intercept.  Same k-mer loop, same order, same float64 sums as that operator, so the result
+ * is bit-identical to casting its output.  This is the row format the sequence kernels' resident cache holds
+ * (complete rows: consumers are told fit_intercept = 0, scale = 1).  A float64 [n, num_rffs] array is never written
+ * for windows (conv_width * C, padded to P) up to 4096 elements: up to 1024 a float32-store mode of wave_conv_kernel,
+ * 2048 / 4096 the same epilogue in wave_tile_conv_kernel.  Wider windows (the any-width path, which keeps its sums in
+ * the float64 output between k-mers) and Rademacher arrays the wave tiles cannot read 16 bytes at a time are STAGED:
+ * the float64 operator runs slice by slice into a float64 area of at most 256 MiB behind the operator's own workspace
+ * and one pass rounds it -- same bits.  Workspace: xgpr_conv_feature_rows_workspace_bytes (covers masks, any-width
+ * scratch, the longest-first order of nseq sequences and the staging area); with less the order is skipped (results
+ * unchanged) and the staged shapes return XGPR_ERR_WORKSPACE, as does a zc that is not 8-byte aligned.  Sequence
+ * lengths are validated on the host before any launch, as for xgpr_conv1d_fgen_f32. */
+size_t xgpr_conv_feature_rows_workspace_bytes(long radem_shape2, long width, long num_rffs, long nseq);
+int xgpr_conv_feature_rows_f32(const float *x, float *zc, const int8_t *radem, const float *chi,
+                               const int32_t *seqlen_host, const int32_t *seqlen_dev,
+                               long n, long L, long C, long num_rffs, long num_freqs, long radem_shape2,
+                               long nseq, int conv_width, int scaling_type, int fit_intercept,
+                               void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- cudaConvGrad (xgpr_cuda_rfgen_cpp_ext.cpp:81-92) */
 int xgpr_conv_grad_f32(const float *x, double *out, double *grad, const int8_t *radem,
                        const float *chi, const int32_t *seqlen_host, const int32_t *seqlen_dev,

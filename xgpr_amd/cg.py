@@ -27,10 +27,27 @@ def rows_ok(kernel):
     return getattr(kernel, "rows_ok", kernel.fused_ok)()
 
 
-def rows_matvec_ok(kernel):
-    """Whether the k = 1 matvec can be applied from this kernel's float32 rows (resident or regenerated): rows_ok, and
-    the streaming kernel (num_freqs <= 16384) or the block contractions (num_rffs % 4 == 0) -- the cache_ok condition."""
-    return rows_ok(kernel) and hasattr(kernel, "cache_ok") and kernel.cache_ok()
+def seq_rows_ok(kernel, dataset=None):
+    """Whether the kernel is a sequence kernel whose float32 feature rows can be regenerated (ConvSORFKernel.seq_rows_ok:
+    Conv1d* / Graph* RBF, Matern, Cauchy on a HIP device) -- and, given a dataset, whether that dataset keeps a resident
+    sigma-scaled shard with its host sequence lengths to regenerate them from (other dataset classes keep their chunk
+    loops over float64 features)."""
+    fn = getattr(kernel, "seq_rows_ok", None)
+    if fn is None or not hasattr(kernel, "fill_feature_rows") or not fn():
+        return False
+    return dataset is None or (hasattr(dataset, "scaled_x") and hasattr(dataset, "get_sequence_lengths"))
+
+
+def any_rows_ok(kernel, dataset=None):
+    """Fixed-vector kernels: ``rows_ok``; sequence kernels: ``seq_rows_ok``."""
+    return rows_ok(kernel) or seq_rows_ok(kernel, dataset)
+
+
+def rows_matvec_ok(kernel, dataset=None):
+    """Whether the k = 1 matvec can be applied from this kernel's float32 rows (resident or regenerated): rows_ok (sequence
+    kernels: seq_rows_ok), and the streaming kernel (num_freqs <= 16384) or the block contractions (num_rffs % 4 == 0) -- the
+    cache_ok condition."""
+    return any_rows_ok(kernel, dataset) and hasattr(kernel, "cache_ok") and kernel.cache_ok()
 
 
 def holds_cache(dataset, kernel):
@@ -39,9 +56,31 @@ def holds_cache(dataset, kernel):
             and getattr(dataset, "_zcache", None) is not None)
 
 
-def row_windows(xs, kernel, holder, window_bytes):
+def window_ranges(n, win, seqlen=None):
+    """(lo, hi, seqlen[lo:hi] or None): contiguous, non-overlapping ranges of at most ``win`` rows that cover range(n), in
+    order.  A window of a sequence shard is a range of sequences and carries the matching slice of the host lengths."""
+    for lo in range(0, n, win):
+        hi = min(n, lo + win)
+        yield lo, hi, (None if seqlen is None else seqlen[lo:hi])
+
+
+def fill_rows(kernel, xs, seqlen, out):
+    """out [w, M] float32 <- the feature rows of the scaled inputs ``xs`` (sequence kernels: with their lengths)."""
+    if seq_rows_ok(kernel):
+        kernel.fill_feature_rows(xs, seqlen, out)
+    else:
+        kernel.fill_feature_cache(xs, out)
+
+
+def shard_lengths(dataset, kernel):
+    """The host sequence lengths a sequence kernel's windows carry; None for the fixed-vector kernels."""
+    return dataset.get_sequence_lengths() if seq_rows_ok(kernel) else None
+
+
+def row_windows(xs, kernel, holder, window_bytes, seqlen=None):
     """(first row, float32 feature rows) over the scaled shard ``xs``, regenerated window by window into one scratch
-    buffer of at most ~``window_bytes`` (kept on ``holder._zwin`` when a holder is given: repeated passes reuse it)."""
+    buffer of at most ~``window_bytes`` (kept on ``holder._zwin`` when a holder is given: repeated passes reuse it).
+    ``seqlen``: the shard's host sequence lengths (sequence kernels, ``shard_lengths``)."""
     n, m = xs.shape[0], kernel.get_num_rffs()
     win = max(1024, min(n, window_bytes // (4 * m)))
     zwin = getattr(holder, "_zwin", None)
@@ -49,10 +88,9 @@ def row_windows(xs, kernel, holder, window_bytes):
         zwin = torch.empty((win, m), dtype=torch.float32, device=xs.device)
         if holder is not None:
             holder._zwin = zwin
-    for lo in range(0, n, win):
-        hi = min(n, lo + win)
+    for lo, hi, lens in window_ranges(n, win, seqlen):
         zc = zwin[:hi - lo]
-        kernel.fill_feature_cache(xs[lo:hi], zc)
+        fill_rows(kernel, xs[lo:hi], lens, zc)
         yield lo, zc
 
 
@@ -65,8 +103,8 @@ def calc_zty(dataset, kernel):
         y = dataset.normalized_y()
         kernel.zty(dataset.scaled_x(kernel.hyperparams[1]), y, z_trans_y)
         y_trans_y = (y ** 2).sum().reshape(1)
-    elif rows_ok(kernel) and torch.device(kernel.device).type == "cuda":
-        # no fused kernel at this width: z^T y from float32 rows -- the resident cache when the dataset holds one,
+    elif any_rows_ok(kernel, dataset) and torch.device(kernel.device).type == "cuda":
+        # no fused kernel at this width / a sequence kernel: z^T y from float32 rows -- the resident cache when the dataset holds one,
         # otherwise windows regenerated into scratch
         y = dataset.normalized_y()
         y_trans_y = (y ** 2).sum().reshape(1)
@@ -78,7 +116,7 @@ def calc_zty(dataset, kernel):
         else:
             part = torch.empty_like(z_trans_y)
             xs = dataset.scaled_x(kernel.hyperparams[1])
-            for lo, zc in row_windows(xs, kernel, None, ConjugateGrad.BLOCK_WINDOW_BYTES):
+            for lo, zc in row_windows(xs, kernel, None, ConjugateGrad.BLOCK_WINDOW_BYTES, shard_lengths(dataset, kernel)):
                 kernel.zty_cached(zc, y[lo:lo + zc.shape[0]], part, ws)
                 z_trans_y += part
     else:
@@ -137,7 +175,7 @@ class ConjugateGrad:
                 self._ws = torch.empty(kernel.workspace_bytes(), dtype=torch.uint8, device=xs.device)
                 self._ws_masks_of = None
             self._matvec_cols(kernel, xs, vec, matvec)
-        elif vec.shape[1] <= 2 and vec.is_cuda and rows_matvec_ok(kernel):
+        elif vec.shape[1] <= 2 and vec.is_cuda and rows_matvec_ok(kernel, dataset):
             # no fused kernel at this width: one column at a time over float32 rows (resident or regenerated)
             tmp = torch.empty(vec.shape[0], dtype=torch.float64, device=vec.device)
             for j in range(vec.shape[1]):
@@ -170,12 +208,12 @@ class ConjugateGrad:
         if not vec.is_contiguous():
             vec = vec.contiguous()
         out = matvec if matvec.is_contiguous() else torch.zeros_like(vec)
-        if self.cache_features and dataset.get_local_ndatapoints() > 0:
+        if (self.cache_features or self._holds_seq_cache(dataset, kernel)) and dataset.get_local_ndatapoints() > 0:
             zc = dataset.feature_cache(kernel)
             kernel.ztz_block_cached(zc, vec, out, self._block_ws(zc.shape[0], kernel, k, vec.device))
-        elif rows_ok(kernel):
+        elif any_rows_ok(kernel, dataset):
             xs = dataset.scaled_x(kernel.hyperparams[1])
-            for _lo, zc in row_windows(xs, kernel, self, self.BLOCK_WINDOW_BYTES):
+            for _lo, zc in row_windows(xs, kernel, self, self.BLOCK_WINDOW_BYTES, shard_lengths(dataset, kernel)):
                 # (per window: a SHORTER last window can need a larger workspace -- the split projection's partials are reserved
                 # for short launches only; _block_ws only grows)
                 kernel.ztz_block_cached(zc, vec, out, self._block_ws(zc.shape[0], kernel, k, vec.device), accumulate=True)
@@ -201,12 +239,12 @@ class ConjugateGrad:
             self._ws_masks_of = None
         if dataset.get_local_ndatapoints() == 0:
             out.zero_()
-        elif self._use_cache(kernel):
+        elif self._use_cache(kernel, dataset):
             kernel.ztz_matvec_cached(dataset.feature_cache(kernel), vec, out, self._ws)
         else:
             xs = dataset.scaled_x(kernel.hyperparams[1])
             part = None
-            for lo, zc in row_windows(xs, kernel, self, self.BLOCK_WINDOW_BYTES):
+            for lo, zc in row_windows(xs, kernel, self, self.BLOCK_WINDOW_BYTES, shard_lengths(dataset, kernel)):
                 if lo == 0:
                     kernel.ztz_matvec_cached(zc, vec, out, self._ws)
                     continue
@@ -221,9 +259,9 @@ class ConjugateGrad:
         if self._ws is None or self._ws.numel() < kernel.workspace_bytes() or self._ws.device != out.device:
             self._ws = torch.empty(kernel.workspace_bytes(), dtype=torch.uint8, device=out.device)
             self._ws_masks_of = None
-        if self._use_cache(kernel):
+        if self._use_cache(kernel, dataset):
             kernel.ztz_matvec_cached(dataset.feature_cache(kernel), vec, out, self._ws)
-        elif not kernel.fused_ok() and rows_matvec_ok(kernel):
+        elif not kernel.fused_ok() and rows_matvec_ok(kernel, dataset):
             self._ztz_rows(dataset, kernel, vec, out)
         else:
             # the Rademacher sign masks are packed into the workspace by the first call only
@@ -236,8 +274,16 @@ class ConjugateGrad:
                 self._ws_masks_of = radem
         self.comm.all_reduce_(out)
 
-    def _use_cache(self, kernel):
-        return self.cache_features and hasattr(kernel, "cache_ok") and kernel.cache_ok()
+    def _use_cache(self, kernel, dataset=None):
+        """The resident cache when ``cache_features`` asks for it -- and, for the sequence kernels, when the dataset already
+        holds it at this sigma (their regenerated windows hold the same rows, at K k-mers x a SORF per sequence)."""
+        if not (hasattr(kernel, "cache_ok") and kernel.cache_ok()):
+            return False
+        return bool(self.cache_features) or self._holds_seq_cache(dataset, kernel)
+
+    @staticmethod
+    def _holds_seq_cache(dataset, kernel):
+        return dataset is not None and seq_rows_ok(kernel) and holds_cache(dataset, kernel)
 
     def _fit_one_rhs_device(self, dataset, kernel, preconditioner, resid, maxiter, tol, verbose, trace):
         """The k = 1 regression solve on the device with the vector updates of
@@ -493,7 +539,7 @@ class ConjugateGrad:
         or (x_k, alphas, betas) with ``nmll_settings``."""
         dev = resid.device
         if (resid.shape[2] == 1 and not nmll_settings and dev.type == "cuda"
-                and (kernel.fused_ok() or rows_matvec_ok(kernel) or self._use_cache(kernel))
+                and (kernel.fused_ok() or rows_matvec_ok(kernel, dataset) or self._use_cache(kernel, dataset))
                 and (preconditioner is None or hasattr(preconditioner, "u_mat"))):
             return self._fit_one_rhs_device(dataset, kernel, preconditioner, resid, maxiter, tol, verbose, trace)
         if (self.BLOCK_DEVICE_SOLVE and 1 < resid.shape[2] <= 32 and dev.type == "cuda" and trace is None

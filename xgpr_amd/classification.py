@@ -19,7 +19,7 @@ from dataclasses import dataclass
 import torch
 
 from . import xgpr_hip_rfgen_ext as ext
-from .cg import _resolve_cache_mode, row_windows, rows_ok
+from .cg import _resolve_cache_mode, any_rows_ok, row_windows, seq_rows_ok, shard_lengths
 from .kernels import block_workspace_bytes
 
 
@@ -63,8 +63,8 @@ class NonlinearCGClassification:
         if self.cache_features:
             yield ds.feature_cache(kernel), labels
             return
-        if rows_ok(kernel):
-            for lo, zc in row_windows(ds.scaled_x(kernel.hyperparams[1]), kernel, self, self.WINDOW_BYTES):
+        if any_rows_ok(kernel, ds):
+            for lo, zc in row_windows(ds.scaled_x(kernel.hyperparams[1]), kernel, self, self.WINDOW_BYTES, shard_lengths(ds, kernel)):
                 yield zc, labels[lo:lo + zc.shape[0]]
             return
         row = 0
@@ -233,11 +233,15 @@ def predict_proba(kernel, weights, gamma, input_x, sequence_lengths=None, chunk_
     icpt, scale = (kernel.fit_intercept, 0.0) if getattr(kernel, "supports_fused", False) else (False, 1.0)
     for i in range(0, input_x.shape[0], chunk_size):
         sl = None if sequence_lengths is None else sequence_lengths[i:i + chunk_size]
-        if getattr(kernel, "supports_fused", False) and kernel.block_ok() and weights.shape[1] <= 32:
+        fused = getattr(kernel, "supports_fused", False)
+        if (fused or (seq_rows_ok(kernel) and sl is not None)) and kernel.block_ok() and weights.shape[1] <= 32:
             from .kernels import scale_input
             xs = scale_input(kernel._as_device_f32(input_x[i:i + chunk_size]), kernel.hyperparams[1])
             zc = torch.empty((xs.shape[0], kernel.get_num_rffs()), dtype=torch.float32, device=kernel.device)
-            kernel.fill_feature_cache(xs, zc)
+            if fused:
+                kernel.fill_feature_cache(xs, zc)
+            else:                                   # sequence kernels: complete float32 rows (icpt False, scale 1 above)
+                kernel.fill_feature_rows(xs, sl, zc)
             pred = torch.empty((xs.shape[0], weights.shape[1]), dtype=torch.float64, device=kernel.device)
             ext.hipZCacheBlockProject(zc, weights, pred, icpt, scale)
         else:

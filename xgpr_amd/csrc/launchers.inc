@@ -315,11 +315,48 @@ int rbf_impl(const T *x, double *out, double *grad, const int8_t *radem, const T
     return launch_generic_sorf<T, MODE_RBF>(a, workspace, wbytes, st);
 }
 
+// ---- float32 feature rows of the sequence kernels (xgpr_conv_feature_rows_f32, mode MODE_CONV_ROWS of conv_impl): outf = zc[n, num_rffs].
+// Windows up to 1024 elements: wave_conv_kernel<LG, CONV_ROWS>; 2048 / 4096: wave_tile_conv_kernel<float, LG, MODE_CONV_ROWS>; every other
+// shape (wider windows, or a Rademacher array the wave tiles cannot read 16 bytes at a time): the float64 operator itself, slice by
+// slice into a float64 staging area behind the operator's own workspace, then one rounding pass -- the any-width kernel keeps its sums
+// in the float64 output between k-mers, so a float32 store there would need a second accumulator scheme for one rarely used path.
+size_t conv_rows_stage_offset(long R, long P, long nseq) {
+    const size_t a = masks_bytes(R), b = generic_scratch_bytes(P, sizeof(float));
+    return align_up((a > b ? a : b) + align_up((size_t)(nseq > 0 ? nseq : 0) * sizeof(int32_t), 256), 256);
+}
+constexpr size_t CONV_ROWS_STAGE_BYTES = (size_t)256 << 20;      // float64 staging of the any-width windows: at most this much is asked for
+
+size_t conv_rows_workspace_bytes(long R, long width, long num_rffs, long nseq) {
+    const long P = padded_width(width);
+    size_t b = conv_rows_stage_offset(R, P, nseq);
+    if (P > 1024 && nseq > 0 && num_rffs > 0) {      // (2048 / 4096 too: the staged route serves them when radem is not 16-byte aligned)
+        const size_t row = (size_t)num_rffs * sizeof(double);
+        size_t rows = CONV_ROWS_STAGE_BYTES / row > 0 ? CONV_ROWS_STAGE_BYTES / row : 1;
+        if (rows > (size_t)nseq) rows = (size_t)nseq;
+        b += align_up(rows * row, 256);
+    }
+    return b;
+}
+
+__global__ __launch_bounds__(256) void round_rows_kernel(const double2 *__restrict__ src, float2 *__restrict__ dst, long npairs,
+                                                         long pairs_per_row, int fit_intercept) {
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= npairs) return;
+    const double2 v = src[idx];
+    const float c = (fit_intercept && idx % pairs_per_row == 0) ? 1.0f : (float)v.x;
+    dst[idx] = make_float2(c, (float)v.y);
+}
+
+int conv_rows_staged(const float *x, float *zc, const int8_t *radem, const float *chi, const int32_t *seqlen_host,
+                     const int32_t *seqlen_dev, long n, long L, long C, long num_rffs, long num_freqs, long R, int conv_width,
+                     int scaling_type, int fit_intercept, void *workspace, size_t wbytes, hipStream_t st);
+
 template <typename T>
 int conv_impl(const T *x, double *out, double *grad, float *outf, const int8_t *radem, const T *chi,
               const int32_t *seqlen_host, const int32_t *seqlen_dev, long n, long L, long C, long out_rows,
               long num_rffs, long grad_rows, long grad_cols, long num_freqs, long R, long nseq, double sigma,
-              int conv_width, int scaling_type, int mode, void *workspace, size_t wbytes, void *stream) {
+              int conv_width, int scaling_type, int mode, void *workspace, size_t wbytes, void *stream, int fit_intercept = 0) {
+    if (mode == MODE_CONV_ROWS && sizeof(T) != 4) return fail(XGPR_ERR_UNSUPPORTED, "float32 feature rows take float32 input");
     if (n == 0 || out_rows != n) return fail(XGPR_ERR_NO_DATAPOINTS, "no datapoints");
     if (num_rffs < 2 || (num_rffs & 1) != 0) return fail(XGPR_ERR_ODD_OUTPUT, "last dim of output must be even number");
     if (mode == MODE_MAXPOOL) {
@@ -340,16 +377,18 @@ int conv_impl(const T *x, double *out, double *grad, float *outf, const int8_t *
     if (rc) return rc;
     if (!seqlen_dev) return fail(XGPR_ERR_WORKSPACE, "seqlen_dev (device copy of the sequence lengths) is required");
     hipStream_t st = (hipStream_t)stream;
+    if (mode == MODE_CONV_ROWS && (!outf || (reinterpret_cast<uintptr_t>(outf) & 7) != 0))
+        return fail(XGPR_ERR_WORKSPACE, "feature rows pointer must be 8-byte aligned");
 
     if constexpr (sizeof(T) == 4) {
         if (P <= 1024) {
-            if (mode != MODE_MAXPOOL && !aligned16(out)) return fail(XGPR_ERR_WORKSPACE, "output pointer must be 16-byte aligned");
+            if (mode != MODE_MAXPOOL && mode != MODE_CONV_ROWS && !aligned16(out)) return fail(XGPR_ERR_WORKSPACE, "output pointer must be 16-byte aligned");
             if (mode == MODE_CONV_GRAD && !aligned16(grad)) return fail(XGPR_ERR_WORKSPACE, "gradient pointer must be 16-byte aligned");
             if (!workspace || wbytes < masks_bytes(R)) return fail(XGPR_ERR_WORKSPACE, "workspace too small (see xgpr_rbf_workspace_bytes)");
             WaveArgs a = {};
             a.x = x; a.out = out; a.outf = outf; a.masks = (const uint64_t *)workspace; a.chi = chi; a.seqlen = seqlen_dev;
             a.n = n; a.row_stride = L * C; a.F = num_freqs; a.d = (int)win; a.kmer_stride = (int)C;
-            a.conv_width = conv_width; a.scaling_type = scaling_type;
+            a.conv_width = conv_width; a.scaling_type = scaling_type; a.fit_intercept = fit_intercept;
             a.MW = masks_per_diag(R); a.nb = (int)((num_freqs + 1023) / 1024);
             a.scale = sqrt(1.0 / (double)num_freqs);
             if (mode == MODE_CONV_GRAD) { a.grad = grad; a.sigma = sigma; }
@@ -373,6 +412,10 @@ int conv_impl(const T *x, double *out, double *grad, float *outf, const int8_t *
 #define CALL_CONV_G(LG) CALL_CONV(LG, CONV_GRAD)
                 DISPATCH_LOG2P(lg, CALL_CONV_G)
 #undef CALL_CONV_G
+            } else if (mode == MODE_CONV_ROWS) {
+#define CALL_CONV_R(LG) CALL_CONV(LG, CONV_ROWS)
+                DISPATCH_LOG2P(lg, CALL_CONV_R)
+#undef CALL_CONV_R
             } else if (mode != MODE_MAXPOOL) {
 #define CALL_CONV_F(LG) CALL_CONV(LG, CONV_FGEN)
                 DISPATCH_LOG2P(lg, CALL_CONV_F)
@@ -391,27 +434,60 @@ int conv_impl(const T *x, double *out, double *grad, float *outf, const int8_t *
     a.x = x; a.out = out; a.grad = grad; a.outf = outf; a.radem = radem; a.chi = chi; a.seqlen = seqlen_dev;
     a.n = n; a.row_stride = L * C; a.F = num_freqs; a.R = R; a.d = (int)win; a.kmer_stride = (int)C;
     a.conv_width = conv_width; a.P = (int)P; a.reps = reps; a.scaling_type = scaling_type;
-    a.nc = norm_constant<T>(P); a.scale = sqrt(1.0 / (double)num_freqs); a.sigma = sigma;
+    a.nc = norm_constant<T>(P); a.scale = sqrt(1.0 / (double)num_freqs); a.sigma = sigma; a.fit_intercept = fit_intercept;
     {
         // wave tiles in registers + an LDS image (wave_tile.inc): float64 input at every padded window width up to 4096, float32 input at
         // 2048 / 4096 (narrower float32 windows were served above); XGPR_F64_PLAN=generic keeps the any-width path (A/B)
         const bool generic64 = wave_tile_plan_off();
         const bool mine = sizeof(T) == 8 ? P <= 4096 : (P > 1024 && P <= 4096);      // (8 / 16 waves per transform leave too few registers for the accumulators)
-        const bool aligned = mode == MODE_MAXPOOL || (aligned16(out) && (mode != MODE_CONV_GRAD || aligned16(grad)));
+        const bool aligned = mode == MODE_MAXPOOL || mode == MODE_CONV_ROWS || (aligned16(out) && (mode != MODE_CONV_GRAD || aligned16(grad)));
         if (mine && !generic64 && aligned && R % 64 == 0 && (reinterpret_cast<uintptr_t>(radem) & 15) == 0) {
             const long items = n * (P > 1024 ? R / 1024 : (num_freqs + 1023) / 1024);
 #define CALL_CONVT(LG) if constexpr ((sizeof(T) == 8 || LG > 10) && LG <= 12) { \
                 using WT = WaveTile<T, LG>; \
                 if (mode == MODE_CONV) return launch_wave_tile(wave_tile_conv_kernel<T, LG, MODE_CONV>, a, items, WT::WAVES, WT::LDS_BYTES, st, "wave_tile_conv_kernel launch"); \
+                if constexpr (sizeof(T) == 4) { if (mode == MODE_CONV_ROWS) return launch_wave_tile(wave_tile_conv_kernel<T, LG, MODE_CONV_ROWS>, a, items, WT::WAVES, WT::LDS_BYTES, st, "wave_tile_conv_kernel launch"); } \
                 if (mode == MODE_CONV_GRAD) return launch_wave_tile(wave_tile_conv_kernel<T, LG, MODE_CONV_GRAD>, a, items, WT::WAVES, WT::LDS_BYTES, st, "wave_tile_conv_kernel launch"); \
                 return launch_wave_tile(wave_tile_conv_kernel<T, LG, MODE_MAXPOOL>, a, items, WT::WAVES, WT::LDS_BYTES, st, "wave_tile_conv_kernel launch"); }
             DISPATCH_LOG2P_WT(ilog2(P), CALL_CONVT)
 #undef CALL_CONVT
         }
     }
+    if (mode == MODE_CONV_ROWS) {
+        if constexpr (sizeof(T) == 4)
+            return conv_rows_staged(x, outf, radem, chi, seqlen_host, seqlen_dev, n, L, C, num_rffs, num_freqs, R, conv_width, scaling_type,
+                                    fit_intercept, workspace, wbytes, st);
+        else return fail(XGPR_ERR_UNSUPPORTED, "float32 feature rows take float32 input");
+    }
     if (mode == MODE_CONV) return launch_generic_sorf<T, MODE_CONV>(a, workspace, wbytes, st);
     if (mode == MODE_CONV_GRAD) return launch_generic_sorf<T, MODE_CONV_GRAD>(a, workspace, wbytes, st);
     return launch_generic_sorf<T, MODE_MAXPOOL>(a, workspace, wbytes, st);
+}
+
+int conv_rows_staged(const float *x, float *zc, const int8_t *radem, const float *chi, const int32_t *seqlen_host,
+                     const int32_t *seqlen_dev, long n, long L, long C, long num_rffs, long num_freqs, long R, int conv_width,
+                     int scaling_type, int fit_intercept, void *workspace, size_t wbytes, hipStream_t st) {
+    const long P = padded_width((long)conv_width * C);
+    const size_t off = conv_rows_stage_offset(R, P, n), row = (size_t)num_rffs * sizeof(double);
+    if (!workspace || !aligned16(workspace) || wbytes < off + row)
+        return fail(XGPR_ERR_WORKSPACE, "workspace too small (see xgpr_conv_feature_rows_workspace_bytes)");
+    double *stage = reinterpret_cast<double *>(reinterpret_cast<unsigned char *>(workspace) + off);
+    long rows = (long)((wbytes - off) / row);
+    if (rows > n) rows = n;
+    for (long lo = 0; lo < n; lo += rows) {
+        const long cnt = n - lo < rows ? n - lo : rows;
+        HIP_TRY(hipMemsetAsync(stage, 0, (size_t)cnt * row, st), "hipMemsetAsync (feature rows staging)");
+        int rc = conv_impl<float>(x + lo * L * C, stage, nullptr, nullptr, radem, chi, seqlen_host + lo, seqlen_dev + lo, cnt, L, C, cnt,
+                                  num_rffs, 0, 0, num_freqs, R, cnt, 0.0, conv_width, scaling_type, MODE_CONV, workspace, off, (void *)st);
+        if (rc) return rc;
+        const long npairs = cnt * (num_rffs / 2);
+        const long nblocks = (npairs + 255) / 256;
+        if (nblocks > 2147483647L) return fail(XGPR_ERR_UNSUPPORTED, "staging slice too large for one rounding launch");
+        hipLaunchKernelGGL(round_rows_kernel, dim3((unsigned)nblocks), dim3(256), 0, st, reinterpret_cast<const double2 *>(stage),
+                           reinterpret_cast<float2 *>(zc + lo * num_rffs), npairs, num_rffs / 2, fit_intercept);
+        HIP_TRY(hipGetLastError(), "round_rows_kernel launch");
+    }
+    return 0;
 }
 
 constexpr long ZTZ_MAX_SLABS = 2048;

@@ -130,7 +130,12 @@ __global__ __launch_bounds__(1024) void conv_order_kernel(const int32_t *__restr
 // MODE: 0 = cudaConv1dFGen, 1 = cudaConv1dMaxpool, 2 = cudaConvGrad -- separate instantiations, so that the
 // 64 extra float64 accumulators of the gradient do not set the register allocation (and with it the occupancy:
 // 1 wave per SIMD when the three shared one function) of the feature operator.
-enum { CONV_FGEN = 0, CONV_MAXPOOL = 1, CONV_GRAD = 2 };
+// MODE 3 = the float32 feature rows (xgpr_conv_feature_rows_f32): CONV_FGEN's front end and k-mer loop unchanged (chi in
+// LDS, laundered sign words, prefetch of the next window, float64 sums in the same order); the epilogue OVERWRITES
+// a.outf[i, 2 f ..] with (float)(0.0 + sum * rs) as (cos, sin) float2 pairs -- what CONV_FGEN leaves in a zeroed float64
+// output, rounded once -- and puts 1.0f into column 0 under fit_intercept.  No load of the old value.
+enum { CONV_FGEN = 0, CONV_MAXPOOL = 1, CONV_GRAD = 2, CONV_ROWS = 3 };
+constexpr bool conv_is_feat(int mode) { return mode == CONV_FGEN || mode == CONV_ROWS; }
 #ifdef XGPR_ABL_NOC2
 #define XGPR_CONV_C2_ALL 0
 #else
@@ -138,7 +143,7 @@ enum { CONV_FGEN = 0, CONV_MAXPOOL = 1, CONV_GRAD = 2 };
 #endif
 
 template <int LOG2P, int MODE>
-__global__ __launch_bounds__(256, (MODE == CONV_GRAD && LOG2P >= 7) ? 1 : (MODE == CONV_FGEN && (LOG2P >= 7 || XGPR_CONV_C2_ALL)) ? 3 : 2) void wave_conv_kernel(WaveArgs a) {
+__global__ __launch_bounds__(256, (MODE == CONV_GRAD && LOG2P >= 7) ? 1 : (conv_is_feat(MODE) && (LOG2P >= 7 || XGPR_CONV_C2_ALL)) ? 3 : 2) void wave_conv_kernel(WaveArgs a) {
     constexpr bool MAXPOOL = MODE == CONV_MAXPOOL;
     const int lane = threadIdx.x & 63;
     const long item = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) + (long)blockIdx.x * 4;
@@ -151,7 +156,7 @@ __global__ __launch_bounds__(256, (MODE == CONV_GRAD && LOG2P >= 7) ? 1 : (MODE 
     // the feature operator on the T path keeps chi (x folded normaliser) in LDS, in the swizzled rows-of-16 image
     // (4 ds_read_b128 per k-mer instead of 16 registers held through the transform): with the sign words laundered
     // below that is what lets it run three waves per SIMD, like the fused matvec (fused_ztz.inc)
-    constexpr bool CHI_LDS = (TP || XGPR_CONV_C2_ALL) && MODE == CONV_FGEN;
+    constexpr bool CHI_LDS = (TP || XGPR_CONV_C2_ALL) && conv_is_feat(MODE);
     // windows of up to 256 elements (BASELINE configs[3]: 9 x 21 = 189): the feature operator's tile leaves the transform
     // in the transposed-columns layout (wave_sorf_c2: no cross-lane stage) -- register r of lane l is frequency
     // 1024 b + c2_elem(l, r), not 1024 b + 64 r + l
@@ -183,7 +188,7 @@ __global__ __launch_bounds__(256, (MODE == CONV_GRAD && LOG2P >= 7) ? 1 : (MODE 
         sw[2] ^= rd_parity<LOG2P>(lane) & 0xffffu;
     }
     // one round's flips through SGPR lane masks (the wave keeps its tile's signs for all k-mers of the sequence)
-    constexpr int C2_MROUND = (C2 && MODE == CONV_FGEN && (LOG2P & 1) == 0) ? 2 : -1;
+    constexpr int C2_MROUND = (C2 && conv_is_feat(MODE) && (LOG2P & 1) == 0) ? 2 : -1;
     uint64_t fmask[16] = {};
     if constexpr (C2_MROUND >= 0) sign_lane_masks(fmask, sw[C2_MROUND]);
     // one k-mer's transform: the tile enters in layout C (the coalesced window) and leaves in C2 / R (windows <= 256) or C with the kept sign
@@ -299,16 +304,36 @@ __global__ __launch_bounds__(256, (MODE == CONV_GRAD && LOG2P >= 7) ? 1 : (MODE 
         double rs = a.scale;
         if (a.scaling_type == 1) rs = a.scale / sqrt((double)nk);
         else if (a.scaling_type == 2) rs = a.scale / (double)nk;
-        double *orow = a.out + i * 2 * a.F;
-        #pragma unroll
-        for (int r = 0; r < 16; r++) {
-            const long f = fe0 + r * FE_STEP;
-            if (f < a.F) {
-                double2 *o = reinterpret_cast<double2 *>(orow + 2 * f);
-                double2 old = *o;
-                old.x += ac[r] * rs;
-                old.y += as[r] * rs;
-                *o = old;
+        if constexpr (MODE == CONV_ROWS) {
+            // Store pattern per instruction (one r, 64 lanes x 8 bytes).  Layout C (windows 512 / 1024): f = 1024 b + 64 r + lane,
+            // 512 contiguous bytes = four whole 128-byte lines.  Layout C2 (128 / 256): f = 1024 b + 256 (lane >> 4) + 16 r + (lane & 15),
+            // four runs of 128 contiguous bytes (sixteen lanes each) 2 KB apart -- whole lines when the row is 128-byte aligned.
+            // Rows layout (<= 64): f = 1024 b + 16 lane + r, 8 bytes per lane 128 bytes apart; the sixteen stores of a lane
+            // complete its line back to back and merge in L2 (the float64 sibling writes 16 bytes 256 apart the same way).
+            float *crow = a.outf + i * 2 * a.F;
+            const bool icpt = a.fit_intercept != 0;
+            #pragma unroll
+            for (int r = 0; r < 16; r++) {
+                const long f = fe0 + r * FE_STEP;
+                if (f < a.F) {
+                    float c = (float)(0.0 + ac[r] * rs);            // (0.0 + x: the sibling's `old + x` on a zeroed output)
+                    const float sv = (float)(0.0 + as[r] * rs);
+                    if (icpt && f == 0) c = 1.0f;
+                    *reinterpret_cast<float2 *>(crow + 2 * f) = make_float2(c, sv);
+                }
+            }
+        } else {
+            double *orow = a.out + i * 2 * a.F;
+            #pragma unroll
+            for (int r = 0; r < 16; r++) {
+                const long f = fe0 + r * FE_STEP;
+                if (f < a.F) {
+                    double2 *o = reinterpret_cast<double2 *>(orow + 2 * f);
+                    double2 old = *o;
+                    old.x += ac[r] * rs;
+                    old.y += as[r] * rs;
+                    *o = old;
+                }
             }
         }
     }

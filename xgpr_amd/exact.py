@@ -26,16 +26,18 @@ def gram_route(dataset, kernel, msub):
         return None
     if not ext.gram_ok(kernel.get_num_rffs(), msub):
         return None
-    from .cg import rows_ok
+    from .cg import rows_ok, seq_rows_ok
     if hasattr(kernel, "fused_ok") and rows_ok(kernel) and hasattr(kernel, "fill_feature_cache"):
         return False
     if hasattr(kernel, "cache_ok") and kernel.cache_ok() and hasattr(kernel, "build_feature_cache"):
         # the resident route pins n_local x M x 4 bytes on the dataset: taken only when the cache is already there or
-        # fits in free HBM with the same headroom rule the solver uses (cg._resolve_cache_mode); otherwise the bounded
-        # chunked float64 formulation
+        # fits in free HBM with the same headroom rule the solver uses (cg._resolve_cache_mode); otherwise regenerated
+        # windows for the sequence kernels, the bounded chunked float64 formulation for the others
         from .cg import _resolve_cache_mode, holds_cache
         if holds_cache(dataset, kernel) or _resolve_cache_mode("auto", kernel, dataset, block=False):
             return True
+    if seq_rows_ok(kernel, dataset):
+        return False
     return None
 
 
@@ -131,21 +133,28 @@ def predict_mean(kernel, weights, input_x, trainy_mean, trainy_std, sequence_len
     ``transform_x`` output."""
     from . import xgpr_hip_rfgen_ext as ext
     preds = []
+    from .cg import seq_rows_ok
     fused = (getattr(kernel, "supports_fused", False) and kernel.block_ok() and hasattr(kernel, "fill_feature_cache")
              and torch.device(kernel.device).type == "cuda")
-    if fused:
+    # the sequence kernels likewise: a chunk's complete float32 rows (intercept column included: no flag, scale 1)
+    seq = not fused and seq_rows_ok(kernel) and kernel.block_ok() and sequence_lengths is not None
+    if fused or seq:
         from .kernels import scale_input
         wcol = weights.to(torch.float64).reshape(-1, 1).contiguous()
     for i in range(0, input_x.shape[0], chunk_size):
-        if fused:
+        sl = None if sequence_lengths is None else sequence_lengths[i:i + chunk_size]
+        if fused or seq:
             xs = scale_input(kernel._as_device_f32(input_x[i:i + chunk_size]), kernel.hyperparams[1])
             zc = torch.empty((xs.shape[0], kernel.get_num_rffs()), dtype=torch.float32, device=kernel.device)
-            kernel.fill_feature_cache(xs, zc)
             pred = torch.empty((xs.shape[0], 1), dtype=torch.float64, device=kernel.device)
-            ext.hipZCacheBlockProject(zc, wcol, pred, kernel.fit_intercept, 0.0)
+            if fused:
+                kernel.fill_feature_cache(xs, zc)
+                ext.hipZCacheBlockProject(zc, wcol, pred, kernel.fit_intercept, 0.0)
+            else:
+                kernel.fill_feature_rows(xs, sl, zc)
+                ext.hipZCacheBlockProject(zc, wcol, pred, False, 1.0)
             preds.append(pred[:, 0])
             continue
-        sl = None if sequence_lengths is None else sequence_lengths[i:i + chunk_size]
         z = kernel.transform_x(input_x[i:i + chunk_size], sl)
         preds.append((z * weights[None, :]).sum(dim=1))
     return torch.cat(preds) * trainy_std + trainy_mean

@@ -326,36 +326,68 @@ class ConvSORFKernel(KernelBase):
     def fused_ok(self):
         return False
 
-    # ---- resident feature cache.  Convolution features cost K k-mers x a full SORF per sequence, so
-    # regenerating them on every CG iteration (what the reference does) is by far the most expensive
-    # way to apply Z; here the shard's Z (kernel_baseclass.py:269-299 output, intercept column set)
-    # is rounded to float32 once -- entries are sums of float32 cos/sin values, so this adds at most
-    # 6e-8 relative per entry -- and streamed from HBM afterwards.
+    # ---- float32 feature rows.  Convolution features cost K k-mers x a full SORF per sequence; the shard's Z
+    # (kernel_baseclass.py:269-299 output, intercept column set) rounded to float32 -- entries are sums of float32
+    # cos/sin values, so this adds at most 6e-8 relative per entry -- is what every solver pass reads: the resident
+    # cache, written once per sigma and streamed from HBM afterwards, or, when it is not kept, windows of rows
+    # regenerated into a reused scratch buffer (cg.row_windows).  Both are written by ``fill_feature_rows``
+    # (hipConvFeatureRows: float32 stores straight from the k-mer loop's float64 sums); float64 Z is only
+    # materialised by ``transform_x`` itself, for callers that ask for it.
     def cache_ok(self):
         return self.num_freqs <= 16384
 
+    def seq_rows_ok(self):
+        """Whether ``fill_feature_rows`` can write this kernel's float32 rows: on a HIP device, for every shape the
+        float64 operator serves."""
+        return torch.device(self.device).type == "cuda"
+
+    def _host_lengths(self, x_scaled, sequence_length):
+        if sequence_length is None:
+            raise RuntimeError("sequence_length is required for convolution kernels.")
+        if x_scaled.shape[2] != self._xdim[2]:
+            raise RuntimeError("Unexpected input shape supplied.")
+        if isinstance(sequence_length, torch.Tensor):
+            sequence_length = sequence_length.cpu().numpy()
+        return np.ascontiguousarray(sequence_length.astype(np.int32, copy=False))
+
+    def fill_feature_rows(self, x_scaled, sequence_length, rows_out):
+        """rows_out [n, num_rffs] float32 <- ``transform_x`` of the (already sigma-scaled, float32) sequences, rounded
+        to float32: overwritten, bit-identical to ``transform_x(...).to(torch.float32)``."""
+        ext.hipConvFeatureRows(x_scaled, rows_out, self.radem_diag, self.chi_arr,
+                               self._host_lengths(x_scaled, sequence_length), self.conv_width, self.scaling_type,
+                               self.fit_intercept)
+
+    def transform_x(self, input_x, sequence_length=None, rows_out=None, pre_scaled=False):
+        """kernel_baseclass.py:269-299 -> float64 [n, M] as for every kernel.  With ``rows_out`` (float32 [n, M] on the
+        device) the same features are written there as float32 rows by ``fill_feature_rows`` -- no float64 array is made --
+        and ``rows_out`` is returned; ``pre_scaled``: ``input_x`` already is the float32 sigma-scaled copy
+        (``dataset.scaled_x``), so it is not scaled again."""
+        if rows_out is None:
+            return super().transform_x(input_x, sequence_length)
+        xin = input_x if pre_scaled else scale_input(self._as_device_f32(input_x), self.hyperparams[1])
+        self.fill_feature_rows(xin, sequence_length, rows_out)
+        return rows_out
+
+    CACHE_BUILD_ROWS = 8192          # sequences per float64 slice where the cache is still the rounding of float64 features
+                                     # (_cache_from_transform_x: a CPU device, a dataset class without a resident shard)
+
     def build_feature_cache(self, dataset):
-        # in windows of up to CACHE_BUILD_ROWS sequences rather than the dataset's chunks (1024 sequences in
-        # BASELINE configs[3]): one wave per (sequence, tile) runs for as long as its sequence has k-mers, and with 3
-        # launch-rounds of waves per chunk the long sequences at the end of a launch leave most of the GPU idle
-        # (3.5 ms per 1024 sequences = 2.9e5 sequences/s against 3.5e5 on 8192-sequence launches)
+        if not hasattr(dataset, "get_xdata") or not hasattr(dataset, "scaled_x") or not self.seq_rows_ok():
+            return _cache_from_transform_x(self, dataset)
+        # one call over the shard: no float64 temporary, and the longest-first order (conv_order_kernel) spans the
+        # whole shard -- a wave runs for as long as its sequence has k-mers, and in the caller's order the long
+        # sequences at the end of a launch leave most of the GPU idle
         n = dataset.get_local_ndatapoints()
         zc = torch.empty((n, self.num_rffs), dtype=torch.float32, device=self.device)
-        if not hasattr(dataset, "get_xdata"):        # any other dataset class: its own chunks
-            lo = 0
-            for xdata, ldata in dataset.get_chunked_x_data():
-                zc[lo:lo + xdata.shape[0]] = self.transform_x(xdata, ldata).to(torch.float32)
-                lo += xdata.shape[0]
-            return zc
-        xall, lall = dataset.get_xdata(), dataset.get_sequence_lengths()
-        step = max(1, min(self.CACHE_BUILD_ROWS, (1 << 30) // (8 * self.num_rffs)))      # float64 temporary <= 1 GiB
-        for lo in range(0, n, step):
-            hi = min(lo + step, n)
-            # (no sequence lengths: transform_x raises the reference's "sequence_length is required" error)
-            zc[lo:hi] = self.transform_x(xall[lo:hi], None if lall is None else lall[lo:hi]).to(torch.float32)
+        if n > 0:
+            # (no sequence lengths: the reference's "sequence_length is required" error)
+            self.transform_x(dataset.scaled_x(self.hyperparams[1]), dataset.get_sequence_lengths(), rows_out=zc,
+                             pre_scaled=True)
         return zc
 
-    CACHE_BUILD_ROWS = 8192
+    def zty_cached(self, zcache, y, out, workspace):
+        """out <- Z^T y from complete float32 rows of this kernel (the resident cache or a regenerated window)."""
+        ext.hipZCacheZtY(zcache, y, out, False, workspace, 1.0)
 
     def ztz_matvec_cached(self, zcache, vec, out, workspace):
         ext.hipZCacheMatvecScaled(zcache, vec, out, 1.0, workspace)
@@ -406,6 +438,29 @@ class ConvSORFKernel(KernelBase):
         ext.hipConv1dFGen(input_x, xtrans, self.radem_diag, self.chi_arr, slen,
                           self.conv_width, self.scaling_type)
         return xtrans
+
+
+def _cache_from_transform_x(kernel, dataset):
+    """The float32 cache of complete feature rows as the rounding of ``transform_x`` output (the two-layer kernel; the
+    sequence kernels on a CPU device or over a dataset class without a resident shard): in windows of up to
+    ``ConvSORFKernel.CACHE_BUILD_ROWS`` sequences rather than the dataset's chunks (1024 sequences in BASELINE configs[3]) -- one wave per
+    (sequence, tile) runs for as long as its sequence has k-mers, and with 3 launch-rounds of waves per chunk the long
+    sequences at the end of a launch leave most of the GPU idle."""
+    n = dataset.get_local_ndatapoints()
+    zc = torch.empty((n, kernel.num_rffs), dtype=torch.float32, device=kernel.device)
+    if not hasattr(dataset, "get_xdata"):        # any other dataset class: its own chunks
+        lo = 0
+        for xdata, ldata in dataset.get_chunked_x_data():
+            zc[lo:lo + xdata.shape[0]] = kernel.transform_x(xdata, ldata).to(torch.float32)
+            lo += xdata.shape[0]
+        return zc
+    xall, lall = dataset.get_xdata(), dataset.get_sequence_lengths()
+    step = max(1, min(ConvSORFKernel.CACHE_BUILD_ROWS, (1 << 30) // (8 * kernel.num_rffs)))      # float64 temporary <= 1 GiB
+    for lo in range(0, n, step):
+        hi = min(lo + step, n)
+        # (no sequence lengths: transform_x raises the reference's "sequence_length is required" error)
+        zc[lo:hi] = kernel.transform_x(xall[lo:hi], None if lall is None else lall[lo:hi]).to(torch.float32)
+    return zc
 
 
 class LinearKernel:
@@ -532,7 +587,9 @@ class Conv1dTwoLayerKernel(KernelBase):
     def block_ok(self):
         return self.num_rffs % 4 == 0
 
-    build_feature_cache = ConvSORFKernel.build_feature_cache
+    def build_feature_cache(self, dataset):
+        return _cache_from_transform_x(self, dataset)
+
     ztz_matvec_cached = ConvSORFKernel.ztz_matvec_cached
     ztz_block_cached = ConvSORFKernel.ztz_block_cached
     cache_rows_to_features = ConvSORFKernel.cache_rows_to_features

@@ -116,6 +116,11 @@ class xGPRegression(_ModelBase):
             raise RuntimeError("Model has not yet been successfully fitted.")
         if get_var and self.var is None:
             raise RuntimeError("Variance was requested but suppress_var was selected when fitting.")
+        if not get_var and sequence_lengths is not None and getattr(self.kernel, "seq_rows_ok", lambda: False)():
+            # sequence kernels, mean only: float32 feature rows through the one-column projection (no float64 features)
+            from .exact import predict_mean
+            return predict_mean(self.kernel, self.weights, input_x, self.trainy_mean, self.trainy_std, sequence_lengths,
+                                chunk_size).cpu().numpy()
         lambda_ = float(self.kernel.get_lambda())
         preds, var = [], []
         for i in range(0, input_x.shape[0], chunk_size):

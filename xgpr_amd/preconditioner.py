@@ -23,7 +23,7 @@ import numpy as np
 import torch
 
 from . import xgpr_hip_rfgen_ext as ext
-from .cg import rows_ok
+from .cg import fill_rows, rows_ok, seq_rows_ok, shard_lengths, window_ranges
 from .kernels import SRHTCompressor
 
 ROW_WINDOW_BYTES = 4 << 30        # float32 feature rows regenerated per window of the accumulation passes
@@ -33,7 +33,8 @@ def _rows_path_ok(dataset, kernel, rank, from_cache, need_bt=False):
     """Whether the accumulation passes can run on float32 feature rows (module docstring)."""
     if not hasattr(kernel, "row_cache_params") or torch.device(kernel.device).type != "cuda":
         return False
-    if not from_cache and not (hasattr(kernel, "fused_ok") and rows_ok(kernel) and hasattr(kernel, "fill_feature_cache")):
+    if not from_cache and not ((hasattr(kernel, "fused_ok") and rows_ok(kernel) and hasattr(kernel, "fill_feature_cache"))
+                               or seq_rows_ok(kernel, dataset)):
         return False
     m = kernel.get_num_rffs()
     if m % 2 != 0 or (need_bt and m % 4 != 0) or not hasattr(dataset, "scaled_x"):
@@ -56,9 +57,8 @@ def _row_windows(dataset, kernel, from_cache, with_y):
     xs = dataset.scaled_x(kernel.hyperparams[1])
     step = min(step, max(n, 1))
     zwin = torch.empty((step, m), dtype=torch.float32, device=xs.device)
-    for lo in range(0, n, step):
-        hi = min(n, lo + step)
-        kernel.fill_feature_cache(xs[lo:hi], zwin[:hi - lo])
+    for lo, hi, lens in window_ranges(n, step, shard_lengths(dataset, kernel)):      # (sequence kernels: windows of sequences with their lengths)
+        fill_rows(kernel, xs[lo:hi], lens, zwin[:hi - lo])
         yield zwin[:hi - lo], (None if yall is None else yall[lo:hi])
 
 
@@ -326,7 +326,14 @@ def subsampled_srht(dataset, kernel, compressor, acc_results, verbose, sample_fr
         cutoff = max(int(sample_frac * float(xdata.shape[0])), 1)
         idx = rng.permutation(xdata.shape[0])[:cutoff]
         tidx = torch.from_numpy(idx).to(xdata.device)
-        zdata = kernel.transform_x(xdata[tidx, ...], None if ldata is None else ldata[idx])
+        if seq_rows_ok(kernel) and ldata is not None:
+            # the sample's float32 feature rows, widened: the float64 convolution operator is not run
+            from .kernels import scale_input
+            rows = torch.empty((cutoff, kernel.get_num_rffs()), dtype=torch.float32, device=kernel.device)
+            kernel.fill_feature_rows(scale_input(kernel._as_device_f32(xdata[tidx, ...]), kernel.hyperparams[1]), ldata[idx], rows)
+            zdata = rows.to(torch.float64)
+        else:
+            zdata = kernel.transform_x(xdata[tidx, ...], None if ldata is None else ldata[idx])
         acc_results += compressor.transform_x(zdata).T @ zdata
         if j % 10 == 0 and verbose:
             print(f"Chunk {j} complete.")

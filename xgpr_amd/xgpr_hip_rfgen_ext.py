@@ -347,6 +347,27 @@ def hipConv1dFGen(inputArr, outputArr, radem, chiArr, seqlengths, convWidth, sca
         radem.shape[2], host.shape[0], int(convWidth), int(scalingType), wp, wn, _stream()))
 
 
+@_array_args("inputArr", "rowsArr", "radem", "chiArr")
+def hipConvFeatureRows(inputArr, rowsArr, radem, chiArr, seqlengths, convWidth, scalingType, fitIntercept):
+    """The float32 feature rows of the sequence kernels (xgpr_conv_feature_rows_f32): rowsArr [N, num_rffs] float32 is
+    OVERWRITTEN with what hipConv1dFGen adds into a zeroed float64 array, rounded once to float32, column 0 set to 1
+    under ``fitIntercept``.  Argument checks as hipConv1dFGen; float32 input only."""
+    x = _dev(inputArr, "inputArr", torch.float32, 3)
+    zc = _dev(rowsArr, "rowsArr", torch.float32, 2)
+    r = _radem3(radem)
+    c = _dev(chiArr, "chiArr", torch.float32, 1)
+    if rowsArr.shape[0] != inputArr.shape[0]:
+        raise RuntimeError("no datapoints")
+    host, dev = _seqlens(seqlengths, inputArr.device)
+    nbytes = _LIB.xgpr_conv_feature_rows_workspace_bytes(radem.shape[2], int(convWidth) * inputArr.shape[2],
+                                                         rowsArr.shape[1], inputArr.shape[0])
+    ws, wp, wn = _workspace(nbytes, inputArr.device)
+    return _lib.check(_LIB.xgpr_conv_feature_rows_f32(
+        x, zc, r, c, C.c_void_p(host.ctypes.data), C.c_void_p(dev.data_ptr()), inputArr.shape[0], inputArr.shape[1],
+        inputArr.shape[2], rowsArr.shape[1], chiArr.shape[0], radem.shape[2], host.shape[0], int(convWidth),
+        int(scalingType), int(bool(fitIntercept)), wp, wn, _stream()))
+
+
 @_array_args("inputArr", "outputArr", "radem", "chiArr", "gradArr")
 def hipConvGrad(inputArr, outputArr, radem, chiArr, seqlengths, gradArr, sigma, convWidth, scalingType):
     """cudaConvGrad (xgpr_cuda_rfgen_cpp_ext.cpp:81-92)."""
