@@ -728,6 +728,59 @@ def g18_cfg5_precond(xgpr):
     save("g18_cfg5_precond.npz", **out)
 
 
+# ---------------------------------------------------------------- G19: the reference's own slow "ground truth" path
+def g19_slow_path(xgpr):
+    """The reference's verbose Python helpers (tests/fht_operations_tests/conv_testing_functions.py: get_features,
+    get_features_with_gradient, get_features_maxpool), imported by path and run unmodified on the inputs of its own
+    get_initial_matrices_fht, in its "float" and "double" precision modes; its cFHT is the reference's compiled transform
+    (the stand-in module registered by import_reference).  Settings of test_conv1d_fht.py:25-28, :51-52, :96-108 and
+    test_maxpool_rfgen.py:23-24, :37-38, four rows each.  The reference's operators are asserted against the slow outputs
+    here at the tolerances of its tests: test_conv1d_fht.py:213-219 (float: rtol 1e-5, atol 1e-5; double: np.allclose
+    defaults) and test_maxpool_rfgen.py:105-111 (float: rtol 1e-6, atol 1e-6; double: defaults)."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location(
+        "conv_testing_functions", "/root/reference/tests/fht_operations_tests/conv_testing_functions.py")
+    ctf = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(ctf)
+    n = 4
+    # kind, kernel_width, num_aas, aa_dim, num_freqs, sigma, normalisation
+    settings = [("conv", 9, 23, 21, 1000, 0.5, 0), ("conv", 5, 56, 2, 62, 0.5, 0), ("conv", 7, 53, 105, 784, 1.0, 1),
+                ("conv", 7, 53, 105, 784, 1.0, 2), ("grad", 9, 23, 21, 128, 0.5, 0), ("maxpool", 9, 23, 21, 130, 1.0, 0),
+                ("maxpool", 5, 56, 2, 62, 1.0, 0)]
+    out = {"n_settings": np.int64(len(settings))}
+    for si, (kind, kw, num_aas, aa_dim, nf, sigma, norm) in enumerate(settings):
+        out.update({f"kind_{si}": np.str_(kind), f"conv_width_{si}": np.int64(kw), f"sigma_{si}": np.float64(sigma),
+                    f"scaling_{si}": np.int64(norm)})
+        for prec, tag in (("float", "32"), ("double", "64")):
+            if (kind, kw, prec) == ("maxpool", 9, "float"):
+                # the reference runs this setting in double only (test_maxpool_rfgen.py:23-28); in float its own operator is
+                # 4e-6 away from its slow path, outside the float tolerance of that file -- no tolerance of the reference's covers
+                # the pair, so it is left out
+                continue
+            dim2, num_blocks, xdata, seqlen, features, s_mat, radem = ctf.get_initial_matrices_fht(
+                n, kw, aa_dim, num_aas, nf, "maxpool" if kind == "maxpool" else "conv", prec)
+            tol = dict(rtol=1e-5, atol=1e-5) if prec == "float" else {}
+            if kind == "conv":
+                slow = ctf.get_features(xdata, kw, dim2, radem, s_mat, nf, num_blocks, sigma, seqlen, prec, norm)
+                REF.cpuConv1dFGen(xdata * sigma, features, radem, s_mat, seqlen, kw, norm)
+                assert np.allclose(slow, features, **tol), (si, prec)
+            elif kind == "grad":
+                slow, slow_grad = ctf.get_features_with_gradient(xdata, kw, dim2, radem, s_mat, nf, num_blocks, sigma, seqlen, prec)
+                grad = np.zeros(features.shape + (1,))
+                REF.cpuConvGrad(xdata, features, radem, s_mat, seqlen, grad, sigma, kw, 0)
+                assert np.allclose(slow, features, **tol) and np.allclose(slow_grad, grad[:, :, 0], **tol), (si, prec)
+                out[f"slowgrad{tag}_{si}"] = slow_grad
+            else:
+                tol = dict(rtol=1e-6, atol=1e-6) if prec == "float" else {}
+                slow = ctf.get_features_maxpool(xdata, kw, dim2, radem, s_mat, nf, num_blocks, seqlen, prec)
+                features = features.astype(np.float32)
+                REF.cpuConv1dMaxpool(xdata, features, radem, s_mat, seqlen, kw)
+                assert np.allclose(slow, features, **tol), (si, prec)
+            out.update({f"x{tag}_{si}": xdata, f"chi{tag}_{si}": s_mat, f"slow{tag}_{si}": slow})
+        out.update({f"radem_{si}": radem, f"seqlen_{si}": seqlen})
+    save("g19_slow_path.npz", **out)
+
+
 def ref_core_digests():
     """ref_core_digests.json: sha256 of every output of tests/test_oracle_vs_ref.py's seeded cases, computed by the
     reference core (the oracle must reproduce them bit for bit where the core cannot be built)."""
@@ -745,7 +798,7 @@ if __name__ == "__main__":
     # python make_golden.py            -> everything;   python make_golden.py g17 g18  -> only the named fixtures
     plain = [g1_fht, g2_rbf, g3_conv, g4_maxpool, g5_srht, ref_core_digests]
     with_ref = [g6_draws, g7_cg, g8_e2e, g9_exact, g10_nmll, g11_classifier, g12_mini_ard, g13_rank_selection,
-                g14_two_layer, g15_crude_tuning, g16_aux, g17_cfg4_conv, g18_cfg5_precond]
+                g14_two_layer, g15_crude_tuning, g16_aux, g17_cfg4_conv, g18_cfg5_precond, g19_slow_path]
     wanted = set(sys.argv[1:])
 
     def selected(fn):

@@ -294,6 +294,10 @@ int rbf_impl(const T *x, double *out, double *grad, const int8_t *radem, const T
         const bool generic64 = wave_tile_plan_off();
         const bool mine = sizeof(T) == 8 ? P <= 8192 : (((want_grad && P > 1024) || P > 4096) && P <= 8192);
         if (mine && !generic64 && R % 64 == 0 && (reinterpret_cast<uintptr_t>(radem) & 15) == 0) {
+            // the gradient mode stores pairs 16 bytes at a time to grad as well as to out (checked above): a grad view that is only
+            // 8-byte aligned gets two 8-byte stores per pair from the same kernel -- the any-width path evaluates cos / sin with the
+            // library's routine, so sending the view there would make the last bit of the result depend on the pointer
+            a.grad_split = want_grad && !aligned16(grad);
             // rbf_ops.cpp:180-185: a double constant in the gradient op
             a.scale = want_grad ? (fit_intercept ? sqrt(1.0 / ((double)num_freqs - 0.5)) : sqrt(1.0 / (double)num_freqs)) : (double)rbf_scale<T>(num_freqs, fit_intercept);
             const long items = n * (P > 1024 ? R / 1024 : (num_freqs + 1023) / 1024);

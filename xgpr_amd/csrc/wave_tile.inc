@@ -273,7 +273,8 @@ __global__ __launch_bounds__(wt_waves(LOG2P) * 64) void wave_tile_rbf_kernel(Sor
             const T gs = sin_val * grad_val, gc = cos_val * grad_val;
             if (f < a.F && live) {
                 *reinterpret_cast<double2 *>(orow + 2 * f) = make_double2(cos_val, sin_val);
-                *reinterpret_cast<double2 *>(grow + 2 * f) = make_double2(-(double)gs, gc);
+                if (a.grad_split) { grow[2 * f] = -(double)gs; grow[2 * f + 1] = gc; }
+                else *reinterpret_cast<double2 *>(grow + 2 * f) = make_double2(-(double)gs, gc);
             }
         }
     } else {
