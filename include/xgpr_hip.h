@@ -112,6 +112,20 @@ int xgpr_rbf_grad_f64(const double *x, double *out, double *grad, const int8_t *
                       double sigma, int fit_intercept,
                       void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- the same gradient operator writing float32 ROWS (kernel_baseclass.py:328-361 gradient_x for the fixed-vector kernels,
+ * sorf_kernel_baseclass.py:136-162; shared_rfgen_ops.cpp:140-155): xgpr_rbf_grad_f32 forms every entry of out and grad in float
+ * and widens it at the store, so float32 rows hold both outputs exactly.  zrows[n, num_rffs] and grows[n, num_rffs] (float32,
+ * row-major, 8-byte aligned) are OVERWRITTEN: (double)zrows == out and (double)grows == grad[:, :, 0] of xgpr_rbf_grad_f32 bit for
+ * bit, except column 0 under fit_intercept, which is 1.0f in zrows and 0.0f in grows (what gradient_x does on the host
+ * afterwards): complete rows -- consumers are told fit_intercept = 0, scale = 1.  Same inputs as xgpr_rbf_grad_f32 (x NOT
+ * pre-multiplied by sigma), workspace xgpr_rbf_workspace_bytes(radem_shape2).  Padded widths up to 8192; beyond, XGPR_ERR_UNSUPPORTED
+ * (the caller keeps xgpr_rbf_grad_f32); a row pointer that is not 8-byte aligned: XGPR_ERR_WORKSPACE.  Nothing is launched
+ * on an error. */
+int xgpr_rbf_grad_rows_f32(const float *x, float *zrows, float *grows, const int8_t *radem, const float *chi,
+                           long n, long d, long num_rffs, long num_freqs, long radem_shape2,
+                           double sigma, int fit_intercept,
+                           void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- cudaConv1dFGen (xgpr_cuda_rfgen_cpp_ext.cpp:70-80): x[n, L, C]; k-mer windows of
  * conv_width*C contiguous elements; results are ADDED into out (which callers zero), as in
  * the reference (rbf_convolution.cu:140-146).  scaling_type 0 none / 1 sqrt / 2 full.
@@ -368,6 +382,17 @@ int xgpr_sketch_gemm_f64(const double *A, long lda, const float *zc, long n, lon
 size_t xgpr_ztz_gram_workspace_bytes(long msub, long n);
 int xgpr_ztz_gram_f64(const float *zc, long n, long num_rffs, double *C, long ldc, long msub, double scale,
                       int fit_intercept, int accumulate, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---- the symmetrised two-operand Gram of the exact NMLL gradient, on the float64 matrix cores:
+ * C[num_rffs, num_rffs] (+)= a^T b + b^T a  (scoring_toolkit/nmll_gradient_tools.py:70 `inner_deriv[:,:,i] += dz_dsigma[:,:,i].T @
+ * xfeatures` over the chunks, then :88 `inner_deriv += transpose(inner_deriv)`), a and b two float32 row arrays [n, num_rffs]
+ * holding COMPLETE rows (xgpr_rbf_grad_rows_f32: no intercept or scale handling here), widened on the way to
+ * v_mfma_f64_16x16x4_f64.  Only tiles on or above the diagonal are computed; both triangles are stored, and the result is
+ * symmetric bit for bit (when accumulating: if C was).  num_rffs a multiple of 128, ldc even >= num_rffs, a / b / C 16-byte
+ * aligned.  Fixed summation order: deterministic.  Workspace: xgpr_cross_gram_workspace_bytes(num_rffs, n). */
+size_t xgpr_cross_gram_workspace_bytes(long num_rffs, long n);
+int xgpr_cross_gram_f64(const float *a, const float *b, long n, long num_rffs, double *C, long ldc, int accumulate,
+                        void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---- cudaMiniARDGrad(inputArr, outputArr, precompWeights, sigmaMap, sigmaVals, gradArr, fitIntercept)
  * (gpu_rf_gen/xgpr_cuda_rfgen_cpp_ext.cpp:50-60; cpu_rf_gen/rbf_ops/ard_ops.cpp:39-124): MiniARD random

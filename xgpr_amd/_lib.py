@@ -25,6 +25,7 @@ SIGNATURES = {
     "xgpr_rbf_feature_gen_f64": [_vp, _vp, _vp, _vp, _l, _l, _l, _l, _l, _l, _i, _vp, _sz, _vp],
     "xgpr_rbf_grad_f32": [_vp, _vp, _vp, _vp, _vp, _l, _l, _l, _l, _l, _l, _l, _l, _d, _i, _vp, _sz, _vp],
     "xgpr_rbf_grad_f64": [_vp, _vp, _vp, _vp, _vp, _l, _l, _l, _l, _l, _l, _l, _l, _d, _i, _vp, _sz, _vp],
+    "xgpr_rbf_grad_rows_f32": [_vp, _vp, _vp, _vp, _vp, _l, _l, _l, _l, _l, _d, _i, _vp, _sz, _vp],
     "xgpr_mini_ard_grad_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _l, _l, _l, _l, _l, _l, _l, _l, _l, _l, _l, _i, _vp],
     "xgpr_mini_ard_grad_f64": [_vp, _vp, _vp, _vp, _vp, _vp, _l, _l, _l, _l, _l, _l, _l, _l, _l, _l, _l, _i, _vp],
     "xgpr_conv1d_fgen_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _l, _l, _l, _l, _l, _l, _l, _l, _i, _i, _vp, _sz, _vp],
@@ -56,6 +57,7 @@ SIGNATURES = {
     "xgpr_srht_sample_rows_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _l, _l, _l, _l, _l, _d, _i, _vp, _sz, _vp],
     "xgpr_sketch_gemm_f64": [_vp, _l, _vp, _l, _l, _vp, _l, _l, _i, _i, _d, _i, _i, _vp, _sz, _vp],
     "xgpr_ztz_gram_f64": [_vp, _l, _l, _vp, _l, _l, _d, _i, _i, _vp, _sz, _vp],
+    "xgpr_cross_gram_f64": [_vp, _vp, _l, _l, _vp, _l, _i, _vp, _sz, _vp],
     "xgpr_selftest_lane_xor": [_vp, _vp],
     "xgpr_ztz_matvec_plan": [_l, _l],
     "xgpr_rccl_load": [C.c_char_p],
@@ -79,6 +81,7 @@ SIZE_FUNCS = {
     "xgpr_srht_sample_workspace_bytes": [_l],
     "xgpr_sketch_gemm_workspace_bytes": [_l, _l, _l, _l, _i],
     "xgpr_ztz_gram_workspace_bytes": [_l, _l],
+    "xgpr_cross_gram_workspace_bytes": [_l, _l],
 }
 STRING_FUNCS = ["xgpr_last_error", "xgpr_build_arch", "xgpr_build_id"]
 

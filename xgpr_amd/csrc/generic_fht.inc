@@ -135,6 +135,7 @@ template <typename T> struct SorfArgs {
     T *scratch;       // GLOBALBUF only: one P-element buffer per workgroup, in global memory
     int fit_intercept;   // MODE_CONV_ROWS only: column 0 of every row is 1.0f
     int grad_split;      // wave_tile_rbf_kernel<.., GRAD>: grad is only 8-byte aligned, its (-sin, cos) pairs go out as two 8-byte stores
+    float *gradf;        // wave_tile_rbf_grad_rows_kernel: the float32 gradient rows (the feature rows go to outf)
 };
 
 // one workgroup per (datapoint i = blockIdx.x, repeat k = blockIdx.y); for the conv ops the

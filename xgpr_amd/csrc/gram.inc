@@ -91,6 +91,8 @@ __global__ __launch_bounds__(512, 4) void gram_lds_kernel(GramArgs a) {
             dma16(aoff_l, abase_g + ch * cstep, lds0 + GR_OFF_A32 + slot * GR_A32 + w * 1024);
             dma16(boff_l, bbase_g + ch * cstep, lds0 + GR_OFF_B32 + slot * GR_B32 + w * 1024);
         };
+        // (cross_gram_lds_kernel, cross_gram.inc, is a COPY of this wait + barrier, of the conversion and of the chunk schedule below: a fix
+        // to the vmcnt / barrier placement or to the schedule is made in both)
 #ifdef XGPR_ABL_GR_NOBAR
         auto landed = [&]() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); };      // (timing ablation, wrong results)
 #else
@@ -149,7 +151,7 @@ __global__ __launch_bounds__(512, 4) void gram_lds_kernel(GramArgs a) {
                 }
             };
             // Operands of k-step q + 1 are read BEFORE the MFMAs of k-step q are issued, and the last k-step of a chunk
-            // runs behind the barrier, after the first reads of the next chunk (as in sketch_gemm_lds_kernel)
+            // runs behind the barrier, after the first reads of the next chunk (as in sketch_gemm_lds_kernel; copied in cross_gram.inc)
             auto chunk = [&](int ch, auto k_tag) {
                 constexpr int K = decltype(k_tag)::value;                  // ch % 6
                 constexpr int slot = K % 3, nslot = (K + 1) % 3, n2slot = (K + 2) % 3, img = K & 1;

@@ -768,6 +768,57 @@ int zcache_build_impl(const float *x, float *zc, const int8_t *radem, const floa
     return 0;
 }
 
+// ---- float32 feature AND gradient rows of the fixed-vector kernels (xgpr_rbf_grad_rows_f32): the float32 gradient operator's kernels
+// (rbf_impl with want_grad: wave_rbf_kernel up to P = 1024, wave tiles at 2048 / 4096 / 8192) with a float2 epilogue into two row arrays.
+// Wider inputs are refused with the feature cache's code for a shape it has no plan for: the caller keeps the float64 operator.
+int rbf_grad_rows_impl(const float *x, float *zrows, float *grows, const int8_t *radem, const float *chi, long n, long d,
+                       long num_rffs, long num_freqs, long R, double sigma, int fit_intercept, void *workspace, size_t wbytes,
+                       void *stream) {
+    const long P = padded_width(d);
+    if (n == 0) return fail(XGPR_ERR_NO_DATAPOINTS, "no datapoints");
+    if (num_rffs < 2 || (num_rffs & 1) != 0) return fail(XGPR_ERR_ODD_OUTPUT, "last dim of output must be even number");
+    if (2 * num_freqs != num_rffs || num_freqs > R) return fail(XGPR_ERR_RFFS_FREQS, "incorrect number of rffs and or freqs.");
+    if (R % P != 0) return fail(XGPR_ERR_RFFS_FREQS, "incorrect number of rffs and or freqs.");
+    if (P > 8192) return fail(XGPR_ERR_UNSUPPORTED, "the gradient rows: no plan at padded width > 8192");
+    if (!zrows || !grows || (reinterpret_cast<uintptr_t>(zrows) & 7) != 0 || (reinterpret_cast<uintptr_t>(grows) & 7) != 0)
+        return fail(XGPR_ERR_WORKSPACE, "row pointers must be 8-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    // rbf_ops.cpp:180-185: a double constant in the gradient op
+    const double scale = fit_intercept ? sqrt(1.0 / ((double)num_freqs - 0.5)) : sqrt(1.0 / (double)num_freqs);
+    if (P <= 1024) {
+        if (!workspace || wbytes < masks_bytes(R)) return fail(XGPR_ERR_WORKSPACE, "workspace too small (see xgpr_rbf_workspace_bytes)");
+        WaveArgs a = {};
+        a.x = x; a.outf = zrows; a.gradf = grows; a.masks = (const uint64_t *)workspace; a.chi = chi;
+        a.n = n; a.row_stride = d; a.F = num_freqs; a.d = (int)d;
+        a.MW = masks_per_diag(R); a.nb = (int)((num_freqs + 1023) / 1024);
+        a.scale = scale; a.sigma = sigma; a.fit_intercept = fit_intercept;
+        const int lg = ilog2(P);
+        fill_norms(a, lg);
+        const long nblocks = (n * a.nb + 3) / 4;
+        if (nblocks > 2147483647L) return fail(XGPR_ERR_UNSUPPORTED, "too many datapoints for one launch");
+        int rc = pack_masks(radem, (uint64_t *)workspace, R, a.MW, st);
+        if (rc) return rc;
+#define CALL_RBFGR(LG) hipLaunchKernelGGL((wave_rbf_kernel<LG, OUT_GRAD_ROWS>), dim3((unsigned)nblocks), dim3(256), 0, st, a)
+        DISPATCH_LOG2P(lg, CALL_RBFGR)
+#undef CALL_RBFGR
+        HIP_TRY(hipGetLastError(), "wave_rbf_kernel (gradient rows) launch");
+        return 0;
+    }
+    if (R % 64 != 0 || (reinterpret_cast<uintptr_t>(radem) & 15) != 0)
+        return fail(XGPR_ERR_UNSUPPORTED, "the gradient rows: the wave tiles read the Rademacher array 16 bytes at a time");
+    SorfArgs<float> s = {};
+    s.x = x; s.outf = zrows; s.gradf = grows; s.radem = radem; s.chi = chi;
+    s.n = n; s.row_stride = d; s.F = num_freqs; s.R = R; s.d = (int)d;
+    s.P = (int)P; s.reps = (int)((num_freqs + P - 1) / P); s.nc = norm_constant<float>(P);
+    s.sigma = sigma; s.scale = scale; s.fit_intercept = fit_intercept;
+    const long items = n * (R / 1024);
+    switch (ilog2(P)) {
+        case 11: return launch_wave_tile(wave_tile_rbf_grad_rows_kernel<11>, s, items, WaveTile<float, 11>::WAVES, WaveTile<float, 11>::LDS_BYTES, st, "wave_tile_rbf_grad_rows_kernel launch");
+        case 12: return launch_wave_tile(wave_tile_rbf_grad_rows_kernel<12>, s, items, WaveTile<float, 12>::WAVES, WaveTile<float, 12>::LDS_BYTES, st, "wave_tile_rbf_grad_rows_kernel launch");
+        default: return launch_wave_tile(wave_tile_rbf_grad_rows_kernel<13>, s, items, WaveTile<float, 13>::WAVES, WaveTile<float, 13>::LDS_BYTES, st, "wave_tile_rbf_grad_rows_kernel launch");
+    }
+}
+
 int zcache_matvec_impl(const float *zc, const double *vec, double *w_out, long n, long num_rffs, int fit_intercept,
                        double scale_override, void *workspace, size_t wbytes, void *stream) {
     if (n == 0) return fail(XGPR_ERR_NO_DATAPOINTS, "no datapoints");
@@ -1333,6 +1384,58 @@ int gram_impl(const float *zc, long n, long num_rffs, double *C, long ldc, long 
         hipLaunchKernelGGL(gram_tail_kernel, dim3((unsigned)((msub + 255) / 256), (unsigned)msub), dim3(256), 0, st,
                            zc + (n - tail) * num_rffs, num_rffs, tail, C, ldc, msub, scale, fit_intercept);
         HIP_TRY(hipGetLastError(), "gram_tail_kernel launch");
+    }
+    return 0;
+}
+
+// ---- A^T B + B^T A on the matrix cores from two float32 row arrays (cross_gram.inc)
+long cross_gram_workgroups(long M, long n) {
+    const long T = M / 128, total = T * (T + 1) / 2 * 2 * (n / 16);
+    long nwg = 2L * device_cus();                     // two 512-thread workgroups per CU, as gram_workgroups
+    if (nwg > total) nwg = total;
+    return nwg > 0 ? nwg : 1;
+}
+size_t cross_gram_workspace_bytes(long M, long n) { return (size_t)cross_gram_workgroups(M, n) * 128 * 128 * sizeof(double); }
+
+int cross_gram_impl(const float *A, const float *B, long n, long num_rffs, double *C, long ldc, int accumulate, void *workspace,
+                    size_t wbytes, void *stream) {
+    const long M = num_rffs;
+    if (n <= 0 || M < 2) return fail(XGPR_ERR_ARRAY_DIMS, "incorrect array dims passed");
+    if (M % 128 != 0) return fail(XGPR_ERR_UNSUPPORTED, "cross gram: num_rffs must be a multiple of 128");
+    if (ldc < M || ldc % 2 != 0) return fail(XGPR_ERR_ARRAY_DIMS, "cross gram: ldc must be even and >= num_rffs");
+    if (!A || !B || !aligned16(A) || !aligned16(B) || !aligned16(C)) return fail(XGPR_ERR_WORKSPACE, "pointers must be 16-byte aligned");
+    if (!workspace || wbytes < cross_gram_workspace_bytes(M, n) || !aligned16(workspace))
+        return fail(XGPR_ERR_WORKSPACE, "workspace too small (see xgpr_cross_gram_workspace_bytes)");
+    hipStream_t st = (hipStream_t)stream;
+    CrossGramArgs a = {};
+    a.A = A; a.B = B; a.ld = M; a.C = C; a.ldc = ldc; a.nchunks = n / 16;
+    a.T = (int)(M / 128); a.ntiles = (long)a.T * (a.T + 1) / 2;
+    a.spill = reinterpret_cast<double *>(workspace);
+    a.accumulate = accumulate;
+    if (a.nchunks > 0) {
+        const long total = a.ntiles * 2 * a.nchunks;
+        long nwg = cross_gram_workgroups(M, n);
+        a.units_per_wg = (total + nwg - 1) / nwg;
+        nwg = (total + a.units_per_wg - 1) / a.units_per_wg;
+        auto kern = cross_gram_lds_kernel;
+        int rc = allow_big_lds(kern, GR_LDS);
+        if (rc) return rc;
+        hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3(512), GR_LDS, st, a);
+        HIP_TRY(hipGetLastError(), "cross_gram_lds_kernel launch");
+        // gram_fixup_kernel as it is: a tile here is a run of 2 nchunks units, its slabs are whole (mirrored) tiles
+        GramArgs f = {};
+        f.C = C; f.ldc = ldc; f.nchunks = 2 * a.nchunks; f.T = a.T; f.ntiles = a.ntiles; f.units_per_wg = a.units_per_wg;
+        f.spill = a.spill;
+        hipLaunchKernelGGL(gram_fixup_kernel, dim3((unsigned)a.ntiles), dim3(256), 0, st, f, nwg);
+        HIP_TRY(hipGetLastError(), "gram_fixup_kernel (cross gram) launch");
+    } else if (!accumulate) {          // fewer rows than one chunk: the tail kernel adds into zeros
+        HIP_TRY(hipMemset2DAsync(C, (size_t)ldc * sizeof(double), 0, (size_t)M * sizeof(double), (size_t)M, st), "cross gram: clearing C");
+    }
+    const int tail = (int)(n % 16);
+    if (tail > 0) {
+        hipLaunchKernelGGL(cross_gram_tail_kernel, dim3((unsigned)((M + 255) / 256), (unsigned)M), dim3(256), 0, st,
+                           A + (n - tail) * M, B + (n - tail) * M, M, tail, C, ldc, M);
+        HIP_TRY(hipGetLastError(), "cross_gram_tail_kernel launch");
     }
     return 0;
 }

@@ -2,7 +2,10 @@
 // ---- cudaRBFFeatureGen: one wave per (datapoint, tile); 4 waves per workgroup.  With CACHE the
 // kernel writes the float32 (cos, sin) pairs before scaling -- the exact values the float64
 // output is the widening of -- into a.outf [n, 2F] (the resident feature cache).
-enum { OUT_F64 = 0, OUT_CACHE = 1, OUT_GRAD = 2 };
+// OUT_GRAD_ROWS (xgpr_rbf_grad_rows_f32): OUT_GRAD's arithmetic with another epilogue -- the float values OUT_GRAD widens at its
+// double2 stores go out as float2 pairs into two float32 row arrays, a.outf (features) and a.gradf (d features / d sigma), with
+// the intercept column written here (1.0f / 0.0f): complete rows, both overwritten.
+enum { OUT_F64 = 0, OUT_CACHE = 1, OUT_GRAD = 2, OUT_GRAD_ROWS = 3 };
 
 template <int LOG2P, int OUT>
 __global__ __launch_bounds__(256) void wave_rbf_kernel(WaveArgs a) {
@@ -55,13 +58,29 @@ __global__ __launch_bounds__(256) void wave_rbf_kernel(WaveArgs a) {
             arg[r] = v[r] * (ch * chs);
         }
     }
-    if constexpr (OUT == OUT_GRAD) {
+    if constexpr (OUT == OUT_GRAD || OUT == OUT_GRAD_ROWS) {
         // cudaRBFGrad: shared_rfgen_ops.cpp:140-155 with its roundings back to float; the input is
         // not pre-multiplied by sigma, and the scale is a double here (rbf_ops.cpp:180-185)
         float gv[16];
         #pragma unroll
         for (int r = 0; r < 16; r++) { gv[r] = arg[r]; arg[r] = (float)(gv[r] * a.sigma); }
         tile_sincos(arg, sn, cs);
+        if constexpr (OUT == OUT_GRAD_ROWS) {
+            float *zrow = a.outf + i * 2 * a.F, *grow = a.gradf + i * 2 * a.F;
+            const bool icpt = a.fit_intercept != 0;
+            #pragma unroll
+            for (int r = 0; r < 16; r++) {
+                const long f = f0 + r * 64;
+                if (full || f < a.F) {
+                    const float cos_val = (float)(cs[r] * a.scale), sin_val = (float)(sn[r] * a.scale);
+                    const float gs = sin_val * gv[r], gc = cos_val * gv[r];
+                    const bool c0 = icpt && f == 0;                 // KernelBase.gradient_x: xtrans[:, 0] = 1, xgrad[:, 0] = 0
+                    *reinterpret_cast<float2 *>(zrow + 2 * f) = make_float2(c0 ? 1.0f : cos_val, sin_val);
+                    *reinterpret_cast<float2 *>(grow + 2 * f) = make_float2(c0 ? 0.0f : -gs, gc);
+                }
+            }
+            return;
+        }
         double *orow = a.out + i * 2 * a.F, *grow = a.grad + i * 2 * a.F;
         #pragma unroll
         for (int r = 0; r < 16; r++) {

@@ -240,7 +240,9 @@ __device__ __forceinline__ bool wt_rbf_front(const SorfArgs<T> &a, T *tbuf, T (&
 
 // T = double: the float64 feature operator (GRAD false) and the float64 gradient operator (GRAD true: cudaRBFGrad, rbf_ops.cpp:112-189,
 // shared_rfgen_ops.cpp:140-155 with its roundings back to T).  T = float, GRAD true: the float32 gradient operator at padded widths
-// 2048 / 4096 (up to 1024 it runs on wave_rbf_kernel<LOG2P, OUT_GRAD>, the feature operator at every width on ztz3_kernel's feature modes).
+// 2048 / 4096 / 8192 (up to 1024 it runs on wave_rbf_kernel<LOG2P, OUT_GRAD>, the feature operator up to 4096 on ztz3_kernel's feature modes).
+// wave_tile_rbf_grad_rows_kernel below repeats the GRAD branch for T = float with a float2 epilogue and is bit-for-bit bound to it
+// (xgpr_rbf_grad_rows_f32): a change to the GRAD arithmetic here is made there too.
 template <typename T, int LOG2P, bool GRAD>
 __global__ __launch_bounds__(wt_waves(LOG2P) * 64) void wave_tile_rbf_kernel(SorfArgs<T> a) {
     using WT = WaveTile<T, LOG2P>;
@@ -256,6 +258,7 @@ __global__ __launch_bounds__(wt_waves(LOG2P) * 64) void wave_tile_rbf_kernel(Sor
     // layout C: register r of lane l is frequency 1024 b + 64 r + l -- one store instruction writes 64 consecutive (cos, sin) pairs
     double *orow = a.out + i * 2 * a.F;
     if constexpr (GRAD) {
+        // (repeated in wave_tile_rbf_grad_rows_kernel: keep the two in step)
         // cudaRBFGrad (shared_rfgen_ops.cpp:140-155): the input is not pre-multiplied by sigma; every product is rounded back to T; the
         // scale is a double constant (rbf_ops.cpp:180-185)
         double *grow = a.grad + i * 2 * a.F;
@@ -309,6 +312,43 @@ __global__ __launch_bounds__(wt_waves(LOG2P) * 64) void wave_tile_rbf_cache_kern
         float sn, cs;
         elem_sincos(v[r], false, sn, cs);                     // (the feature mode's call for T = float)
         if (f < a.F && live) *reinterpret_cast<float2 *>(orow + 2 * f) = make_float2(cs, sn);
+    }
+}
+
+// The float32 feature and gradient rows (xgpr_rbf_grad_rows_f32) at padded widths 2048 / 4096 / 8192: the front and the float products of
+// wave_tile_rbf_kernel<float, LOG2P, true> expression for expression -- (float)(v * sigma), elem_sincos, (float)(cs * scale), sin_val *
+// grad_val -- with the values that kernel widens at its double2 stores written as float2 pairs into a.outf[i, 2 f ..] (features) and
+// a.gradf[i, 2 f ..] (d features / d sigma); column 0 is 1.0f / 0.0f under fit_intercept.  Complete rows, both overwritten.
+template <int LOG2P>
+__global__ __launch_bounds__(wt_waves(LOG2P) * 64) void wave_tile_rbf_grad_rows_kernel(SorfArgs<float> a) {
+    using WT = WaveTile<float, LOG2P>;
+    static_assert(WT::WIDE, "the gradient rows up to P = 1024 run on wave_rbf_kernel<LOG2P, OUT_GRAD_ROWS>");
+    extern __shared__ __attribute__((aligned(16))) unsigned char wt_lds[];
+    float *tbuf = reinterpret_cast<float *>(wt_lds);
+    const int lane = threadIdx.x & 63;
+    float v[16];
+    long i;
+    int b;
+    const bool live = wt_rbf_front<float, LOG2P>(a, tbuf, v, i, b);
+    float *zrow = a.outf + i * 2 * a.F, *grow = a.gradf + i * 2 * a.F;
+    float pv[16];
+    #pragma unroll
+    for (int r = 0; r < 16; r++) pv[r] = (float)(v[r] * a.sigma);
+    const bool big = tile_has_big(pv);                           // (false for float: the sibling's call, kept in the same form)
+    const bool icpt = a.fit_intercept != 0;
+    #pragma unroll
+    for (int r = 0; r < 16; r++) {
+        const long f = (long)b * 1024 + 64 * r + lane;
+        const float grad_val = v[r];
+        float sn, cs;
+        elem_sincos(pv[r], big, sn, cs);
+        const float cos_val = (float)(cs * a.scale), sin_val = (float)(sn * a.scale);
+        const float gs = sin_val * grad_val, gc = cos_val * grad_val;
+        if (f < a.F && live) {
+            const bool c0 = icpt && f == 0;
+            *reinterpret_cast<float2 *>(zrow + 2 * f) = make_float2(c0 ? 1.0f : cos_val, sin_val);
+            *reinterpret_cast<float2 *>(grow + 2 * f) = make_float2(c0 ? 0.0f : -gs, gc);
+        }
     }
 }
 

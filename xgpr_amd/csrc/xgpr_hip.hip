@@ -57,6 +57,7 @@ namespace {
 #include "zblock.inc"
 #include "sketch_gemm.inc"
 #include "gram.inc"
+#include "cross_gram.inc"
 #include "mini_ard.inc"
 #include "cg_kernels.inc"
 #include "launchers.inc"
@@ -119,6 +120,12 @@ int xgpr_rbf_grad_f32(const float *x, double *out, double *grad, const int8_t *r
                       void *stream) {
     return rbf_impl<float>(x, out, grad, radem, chi, n, d, out_rows, num_rffs, grad_rows, grad_cols, num_freqs,
                            radem_shape2, sigma, fit_intercept, true, workspace, workspace_bytes, stream);
+}
+int xgpr_rbf_grad_rows_f32(const float *x, float *zrows, float *grows, const int8_t *radem, const float *chi, long n,
+                           long d, long num_rffs, long num_freqs, long radem_shape2, double sigma, int fit_intercept,
+                           void *workspace, size_t workspace_bytes, void *stream) {
+    return rbf_grad_rows_impl(x, zrows, grows, radem, chi, n, d, num_rffs, num_freqs, radem_shape2, sigma, fit_intercept,
+                              workspace, workspace_bytes, stream);
 }
 int xgpr_rbf_grad_f64(const double *x, double *out, double *grad, const int8_t *radem, const double *chi, long n,
                       long d, long out_rows, long num_rffs, long grad_rows, long grad_cols, long num_freqs,
@@ -248,6 +255,12 @@ size_t xgpr_ztz_gram_workspace_bytes(long msub, long n) { return gram_workspace_
 int xgpr_ztz_gram_f64(const float *zc, long n, long num_rffs, double *C, long ldc, long msub, double scale,
                       int fit_intercept, int accumulate, void *workspace, size_t workspace_bytes, void *stream) {
     return gram_impl(zc, n, num_rffs, C, ldc, msub, scale, fit_intercept, accumulate, workspace, workspace_bytes, stream);
+}
+
+size_t xgpr_cross_gram_workspace_bytes(long num_rffs, long n) { return cross_gram_workspace_bytes(num_rffs, n); }
+int xgpr_cross_gram_f64(const float *a, const float *b, long n, long num_rffs, double *C, long ldc, int accumulate,
+                        void *workspace, size_t workspace_bytes, void *stream) {
+    return cross_gram_impl(a, b, n, num_rffs, C, ldc, accumulate, workspace, workspace_bytes, stream);
 }
 
 int xgpr_cg_step1_f64(double *w, const double *p, double *x, const double *r, double *r_next, const double *z,

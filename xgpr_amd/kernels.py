@@ -211,6 +211,20 @@ class SORFKernel(KernelBase):
         path beyond).  There the solver's passes read regenerated rows or the resident cache instead of float64 Z."""
         return self.fused_ok() or (padded_dims(self._xdim[-1]) > FUSED_MAX_WIDTH and self.num_freqs <= 65536)
 
+    def grad_rows_ok(self):
+        """Whether ``fill_grad_rows`` can write this kernel's float32 feature AND gradient rows, and the exact NMLL
+        gradient's accumulations can run on them (nmll.calc_gradient_terms): a HIP device, ``rows_ok``, padded width up
+        to 8192 (wider inputs keep the float64 gradient operator) and whole 128 x 128 tiles for the two Gram kernels."""
+        return (torch.device(self.device).type == "cuda" and self.rows_ok()
+                and padded_dims(self._xdim[-1]) <= ext.GRAD_ROWS_MAX_WIDTH and ext.cross_gram_ok(self.num_rffs)
+                and self.radem_diag.data_ptr() % 16 == 0)
+
+    def fill_grad_rows(self, x_unscaled, zrows, grows):
+        """zrows, grows [w, M] float32 <- the complete feature rows and d(features)/d(sigma) rows of the UNSCALED float32
+        inputs (what ``gradient_x`` returns, exactly: every entry of it is a float32 value); intercept column included."""
+        ext.hipRBFGradRows(x_unscaled, zrows, grows, self.radem_diag, self.chi_arr, float(self.hyperparams[1]),
+                           self.fit_intercept)
+
     def zty_cached(self, zcache, y, out, workspace):
         """out <- Z^T y from float32 rows of this kernel (the resident cache or a regenerated window)."""
         ext.hipZCacheZtY(zcache, y, out, self.fit_intercept, workspace)

@@ -142,9 +142,9 @@ class xGPRegression(_ModelBase):
         self.set_hyperparams(hyperparams, dataset)
         return _nmll.exact_nmll(self.kernel, dataset)
 
-    def exact_nmll_gradient(self, hyperparams, dataset):
+    def exact_nmll_gradient(self, hyperparams, dataset, subsample=1):
         self.set_hyperparams(hyperparams, dataset)
-        return _nmll.exact_nmll_gradient(self.kernel, dataset)
+        return _nmll.exact_nmll_gradient(self.kernel, dataset, subsample)
 
     def approximate_nmll(self, hyperparams, dataset, manual_settings=None):
         self.set_hyperparams(hyperparams, dataset)

@@ -2,15 +2,17 @@
 quadrature) form that drives hyperparameter tuning -- the "next" rows 1 and 2 of SURVEY.md
 section 8f.  They reuse the hot path unchanged: the approximate NMLL is one preconditioned CG solve
 with k = nsamples + 1 = 26 right-hand sides, whose block matvec runs on the float64 matrix cores
-(hipZCacheBlockMatvec); the gradient terms are the gradient operators (hipRBFGrad / hipConvGrad)
-followed by dense M x M accumulations.
+(hipZCacheBlockMatvec); the gradient terms of the fixed-vector kernels are accumulated from float32
+feature and gradient rows (hipRBFGradRows) by the two Gram kernels on the same matrix cores
+(hipZtZGram, hipCrossGram), those of the other kernels are the gradient operators (hipConvGrad,
+hipMiniARDGrad, ...) followed by dense M x M accumulations.
 
   * ``optimize_alpha_beta``     <-> scoring_toolkit/alpha_beta_optimizer.py:13-39
   * ``generate_normal_probes``  <-> scoring_toolkit/probe_generators.py:9-30 (gpu) / :54-75 (cpu)
   * ``estimate_logdet``         <-> scoring_toolkit/approximate_nmll_calcs.py:12-50
   * ``approximate_nmll``        <-> xgp_regression.py:264-367
   * ``exact_nmll``              <-> xgp_regression.py:152-205
-  * ``calc_gradient_terms``     <-> scoring_toolkit/nmll_gradient_tools.py:12-93 (subsample = 1)
+  * ``calc_gradient_terms``     <-> scoring_toolkit/nmll_gradient_tools.py:12-93
   * ``exact_nmll_reg_grad``     <-> scoring_toolkit/nmll_gradient_tools.py:97-162
   * ``exact_nmll_gradient``     <-> xgp_regression.py:209-260
 
@@ -126,8 +128,74 @@ def exact_nmll(kernel, dataset):
     return float(negloglik)
 
 
-def calc_gradient_terms(dataset, kernel):
-    """nmll_gradient_tools.py:12-93 with subsample = 1; partial sums are all-reduced over ranks."""
+def _check_subsample(subsample):
+    if subsample > 1 or subsample < 0.01:
+        raise RuntimeError("Subsample must be in the range [0.01, 1].")
+
+
+def _grad_rows_route(dataset, kernel):
+    """Whether the gradient terms are accumulated from float32 feature and gradient rows: the fixed-vector kernels on a
+    HIP device wherever ``SORFKernel.grad_rows_ok``, over a shard the writer can read as it is (float32, 2-d, on the
+    device; anything else goes through the float64 formulation, which converts each chunk)."""
+    fn = getattr(kernel, "grad_rows_ok", None)
+    if fn is None or not hasattr(dataset, "get_xdata") or not fn():
+        return False
+    xall = dataset.get_xdata()
+    return (isinstance(xall, torch.Tensor) and xall.is_cuda and xall.dtype == torch.float32 and xall.dim() == 2
+            and xall.is_contiguous())
+
+
+def _grad_window_rows(m):
+    """Rows per window of the rows route: the TWO float32 row windows together stay within the budget of one window of
+    the other accumulation passes (preconditioner.ROW_WINDOW_BYTES); whole groups of 4 rows."""
+    from .preconditioner import ROW_WINDOW_BYTES
+    return max(4096, ROW_WINDOW_BYTES // (8 * m)) // 4 * 4
+
+
+def _gradient_terms_rows(dataset, kernel, z_trans_z, z_trans_y, dz_dsigma_ty, inner_deriv, y_trans_y):
+    """The accumulations of calc_gradient_terms over windows of float32 rows: Z^T Z and the symmetrised dZ^T Z + Z^T dZ
+    on the float64 matrix cores (xgpr_ztz_gram_f64, xgpr_cross_gram_f64), Z^T y and dZ^T y by the one-column
+    back-projection.  float64 Z / dZ and the M x M GEMM temporaries are never written; ``inner_deriv`` comes out
+    symmetrised."""
+    from . import xgpr_hip_rfgen_ext as ext
+    m = kernel.get_num_rffs()
+    xall = dataset.get_xdata()
+    n = xall.shape[0]
+    if n == 0:
+        return
+    yall = dataset.normalized_y()
+    step = min(_grad_window_rows(m), n)
+    dev = z_trans_z.device
+    zwin = torch.empty((step, m), dtype=torch.float32, device=dev)
+    gwin = torch.empty((step, m), dtype=torch.float32, device=dev)
+    gws = cws = bws = None
+    inner = inner_deriv[:, :, 0]
+    for lo in range(0, n, step):
+        hi = min(n, lo + step)
+        zr, gr = zwin[:hi - lo], gwin[:hi - lo]
+        kernel.fill_grad_rows(xall[lo:hi], zr, gr)
+        yw = yall[lo:hi]
+        ycol = yw.reshape(-1, 1).contiguous()
+        need = ext.zcache_block_workspace_bytes(hi - lo, m, 1)
+        if bws is None or bws.numel() < need:
+            bws = torch.empty(need, dtype=torch.uint8, device=dev)
+        gws = ext.hipZtZGram(zr, z_trans_z, False, 1.0, accumulate=True, workspace=gws)
+        cws = ext.hipCrossGram(gr, zr, inner, accumulate=True, workspace=cws)
+        ext.hipZCacheBlockBackproject(zr, ycol, z_trans_y.reshape(-1, 1), False, bws, 1.0, accumulate=True)
+        ext.hipZCacheBlockBackproject(gr, ycol, dz_dsigma_ty, False, bws, 1.0, accumulate=True)
+        y_trans_y += yw @ yw
+
+
+def calc_gradient_terms(dataset, kernel, subsample=1):
+    """nmll_gradient_tools.py:12-93; partial sums are all-reduced over ranks.  ``subsample`` in [0.01, 1]: the fraction
+    of every chunk's rows that is used, drawn as the reference draws it (one generator seeded with 123, one
+    ``choice`` without replacement per chunk, in chunk order); the last value returned is the number of rows used.
+
+    The fixed-vector kernels on a HIP device (``SORFKernel.grad_rows_ok``) accumulate all terms from float32 feature
+    and gradient rows (``_gradient_terms_rows``); everything else -- sequence kernels, MiniARD, two-layer, linear, CPU
+    tensors, feature counts that are not a multiple of 128, padded widths beyond 8192, and every subsampled
+    evaluation -- keeps the chunked float64 formulation."""
+    _check_subsample(subsample)
     comm = dataset.comm
     num_rffs = kernel.get_num_rffs()
     nkern = kernel.get_hyperparams().shape[0] - 1
@@ -137,18 +205,36 @@ def calc_gradient_terms(dataset, kernel):
     dz_dsigma_ty = torch.zeros((num_rffs, nkern), **f64)
     inner_deriv = torch.zeros((num_rffs, num_rffs, nkern), **f64)
     y_trans_y = torch.zeros(1, **f64)
-    for xin, yin, ldata in dataset.get_chunked_data():
-        xfeatures, dz_dsigma, ydata = kernel.gradient_x_y(xin, yin, ldata)
-        z_trans_y += xfeatures.T @ ydata
-        z_trans_z += xfeatures.T @ xfeatures
-        y_trans_y += ydata @ ydata
-        for i in range(dz_dsigma.shape[2]):
-            dz_dsigma_ty[:, i] += dz_dsigma[:, :, i].T @ ydata
-            inner_deriv[:, :, i] += dz_dsigma[:, :, i].T @ xfeatures
+    rows_route = subsample == 1 and nkern == 1 and _grad_rows_route(dataset, kernel)
+    ndatapoints = dataset.get_ndatapoints()
+    if rows_route:
+        _gradient_terms_rows(dataset, kernel, z_trans_z, z_trans_y, dz_dsigma_ty, inner_deriv, y_trans_y)
+    else:
+        rng = np.random.default_rng(123) if subsample != 1 else None
+        nused = 0
+        for xin, yin, ldata in dataset.get_chunked_data():
+            if rng is not None:
+                idx = rng.choice(xin.shape[0], max(1, int(subsample * xin.shape[0])), replace=False)
+                tidx = torch.from_numpy(idx).to(xin.device)
+                xin, yin = xin[tidx, ...], yin[tidx]
+                ldata = None if ldata is None else ldata[idx]
+                nused += xin.shape[0]
+            xfeatures, dz_dsigma, ydata = kernel.gradient_x_y(xin, yin, ldata)
+            z_trans_y += xfeatures.T @ ydata
+            z_trans_z += xfeatures.T @ xfeatures
+            y_trans_y += ydata @ ydata
+            for i in range(dz_dsigma.shape[2]):
+                dz_dsigma_ty[:, i] += dz_dsigma[:, :, i].T @ ydata
+                inner_deriv[:, :, i] += dz_dsigma[:, :, i].T @ xfeatures
+        if rng is not None:
+            count = torch.tensor([float(nused)], **f64)
+            comm.all_reduce_(count)
+            ndatapoints = int(round(count.item()))
     for t in (z_trans_z, z_trans_y, dz_dsigma_ty, inner_deriv, y_trans_y):
         comm.all_reduce_(t)
-    inner_deriv += inner_deriv.transpose(0, 1).clone()
-    return z_trans_z, z_trans_y, float(y_trans_y.item()), dz_dsigma_ty, inner_deriv, dataset.get_ndatapoints()
+    if not rows_route:
+        inner_deriv += inner_deriv.transpose(0, 1).clone()
+    return z_trans_z, z_trans_y, float(y_trans_y.item()), dz_dsigma_ty, inner_deriv, ndatapoints
 
 
 def exact_nmll_reg_grad(z_trans_z, z_trans_y, y_trans_y, hparams, ndatapoints, dz_dsigma_ty, inner_deriv):
@@ -183,10 +269,11 @@ def exact_nmll_reg_grad(z_trans_z, z_trans_y, y_trans_y, hparams, ndatapoints, d
     return negloglik, grad, beta
 
 
-def exact_nmll_gradient(kernel, dataset):
-    """xgp_regression.py:209-260 for a kernel whose hyperparameters are already set."""
+def exact_nmll_gradient(kernel, dataset, subsample=1):
+    """xgp_regression.py:209-260 for a kernel whose hyperparameters are already set; ``subsample``: see
+    ``calc_gradient_terms``."""
     hparams = kernel.get_hyperparams(logspace=False)
-    terms = calc_gradient_terms(dataset, kernel)
+    terms = calc_gradient_terms(dataset, kernel, subsample)
     z_trans_z, z_trans_y, y_trans_y, dz_dsigma_ty, inner_deriv, nsamples = terms
     negloglik, grad, _ = exact_nmll_reg_grad(z_trans_z, z_trans_y, y_trans_y, hparams, nsamples,
                                              dz_dsigma_ty, inner_deriv)

@@ -268,6 +268,35 @@ def hipZtZGram(cacheArr, outArr, fitIntercept, scale=0.0, accumulate=False, work
     return workspace
 
 
+def cross_gram_ok(num_rffs):
+    """Shapes hipCrossGram covers: whole 128 x 128 tiles (the rule of ``gram_ok`` with msub = num_rffs)."""
+    return gram_ok(num_rffs, num_rffs)
+
+
+def hipCrossGram(aRows, bRows, outArr, accumulate=False, workspace=None):
+    """``outArr[M, M] (+)= aRows.T @ bRows + bRows.T @ aRows`` on the float64 matrix cores from two float32 row arrays
+    [n, M] of complete rows (nmll_gradient_tools.py:70 and :88: ``inner_deriv`` after its symmetrisation).  ``outArr``
+    is float64 with unit column stride: a contiguous [M, ldc >= M] array or an [M, M] view of one.  Symmetric bit
+    for bit, deterministic.  Returns the workspace used (pass it back in to avoid reallocation)."""
+    a = _dev(aRows, "aRows", torch.float32, 2)
+    b = _dev(bRows, "bRows", torch.float32, 2)
+    if not isinstance(outArr, torch.Tensor) or not outArr.is_cuda or outArr.dtype != torch.float64 or outArr.dim() != 2:
+        raise TypeError("outArr: expected a 2-d float64 device tensor")
+    n, m = aRows.shape
+    if tuple(bRows.shape) != (n, m):
+        raise TypeError("aRows / bRows: expected the same shape")
+    if outArr.stride(1) != 1 or outArr.shape[0] != m or outArr.shape[1] < m or outArr.stride(0) < outArr.shape[1]:
+        raise TypeError("outArr: expected [M, >= M] with unit column stride")
+    if not cross_gram_ok(m):
+        raise RuntimeError("incorrect array dims passed")
+    need = int(_LIB.xgpr_cross_gram_workspace_bytes(m, n))
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=aRows.device)
+    _lib.check(_LIB.xgpr_cross_gram_f64(a, b, n, m, C.c_void_p(outArr.data_ptr()), outArr.stride(0), int(bool(accumulate)),
+                                        C.c_void_p(workspace.data_ptr()), C.c_size_t(workspace.numel()), _stream()))
+    return workspace
+
+
 def sketch_gemm_workspace_bytes(nrows, jdim, kdim, ldc, trans_out):
     return int(_LIB.xgpr_sketch_gemm_workspace_bytes(nrows, jdim, kdim, ldc, int(bool(trans_out))))
 
@@ -312,6 +341,33 @@ def hipRBFGrad(inputArr, outputArr, gradArr, radem, chiArr, sigma, fitIntercept)
         x, o, g, r, c, inputArr.shape[0], inputArr.shape[1], outputArr.shape[0], outputArr.shape[1],
         gradArr.shape[0], gradArr.shape[1], chiArr.shape[0], radem.shape[2], float(sigma),
         int(bool(fitIntercept)), wp, wn, _stream()))
+
+
+GRAD_ROWS_MAX_WIDTH = 8192      # padded input width up to which xgpr_rbf_grad_rows_f32 has a plan
+
+
+def hipRBFGradRows(inputArr, zRows, gRows, radem, chiArr, sigma, fitIntercept):
+    """cudaRBFGrad writing float32 rows: ``zRows[N, M]`` and ``gRows[N, M]`` (float32, 8-byte aligned, unit column
+    stride, rows of M floats apart; both overwritten) hold what hipRBFGrad writes to ``outputArr`` and
+    ``gradArr[:, :, 0]`` -- every entry of those is a float32 value -- with column 0 set to 1 / 0 under fitIntercept:
+    complete rows (see include/xgpr_hip.h)."""
+    x = _dev(inputArr, "inputArr", torch.float32, 2)
+    r = _radem3(radem)
+    c = _dev(chiArr, "chiArr", torch.float32, 1)
+    n = inputArr.shape[0]
+    for t, nm in ((zRows, "zRows"), (gRows, "gRows")):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or t.dim() != 2:
+            raise TypeError(f"{nm}: expected a 2-d float32 device tensor")
+        if t.shape[0] != n:
+            raise RuntimeError("no datapoints")
+        if t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) != t.shape[1]):
+            raise TypeError(f"{nm}: expected rows of M contiguous floats, M floats apart")
+    if tuple(gRows.shape) != tuple(zRows.shape):
+        raise RuntimeError("Wrong array sizes.")
+    ws, wp, wn = _sorf_ws(radem, inputArr.shape[1], inputArr)
+    return _lib.check(_LIB.xgpr_rbf_grad_rows_f32(
+        x, C.c_void_p(zRows.data_ptr()), C.c_void_p(gRows.data_ptr()), r, c, n, inputArr.shape[1], zRows.shape[1],
+        chiArr.shape[0], radem.shape[2], float(sigma), int(bool(fitIntercept)), wp, wn, _stream()))
 
 
 @_array_args("inputArr", "outputArr", "precompWeights", "sigmaMap", "sigmaVals", "gradArr")
