@@ -183,6 +183,28 @@ int xgpr_conv_grad_f64(const double *x, double *out, double *grad, const int8_t 
                        double sigma, int conv_width, int scaling_type,
                        void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- the same gradient operator writing float32 ROWS (kernel_baseclass.py:328-361 gradient_x for the sequence kernels,
+ * conv_kernel_baseclass.py:157-190).  Inputs of xgpr_conv_grad_f32 (x NOT pre-multiplied by sigma) plus fit_intercept.
+ * zrows[n, num_rffs] and grows[n, num_rffs] (float32, row-major, 8-byte aligned) are OVERWRITTEN -- no zero fill needed --
+ * with exactly what xgpr_conv_grad_f32 adds into zeroed float64 out and grad[:, :, 0], rounded once to float32 (round to
+ * nearest even): same k-mer loop, same order, same per-k-mer roundings to float, same float64 sums, so the result is
+ * bit-identical to casting that operator's outputs.  Under fit_intercept column 0 is 1.0f in zrows and 0.0f in grows (what
+ * gradient_x does on the host afterwards): complete rows -- consumers are told fit_intercept = 0, scale = 1.  No float64
+ * [n, num_rffs] array is written for windows (conv_width * C, padded to P) up to 4096 elements: up to 1024 a float32-store
+ * mode of wave_conv_kernel, 2048 / 4096 the same epilogue in wave_tile_conv_kernel.  Wider windows and Rademacher arrays
+ * the wave tiles cannot read 16 bytes at a time are STAGED: xgpr_conv_grad_f32 runs slice by slice into two float64 areas
+ * (out, grad) of together at most 256 MiB behind the operator's own workspace and one pass each rounds them -- same bits.
+ * Workspace: xgpr_conv_grad_rows_workspace_bytes (covers masks, any-width scratch, the longest-first order of nseq
+ * sequences and the staging area); with less the order is skipped (results unchanged) and the staged shapes return
+ * XGPR_ERR_WORKSPACE, as does a row pointer that is not 8-byte aligned.  Sequence lengths are validated on the host before
+ * any launch, as for xgpr_conv_grad_f32; nothing is launched on an error. */
+size_t xgpr_conv_grad_rows_workspace_bytes(long radem_shape2, long width, long num_rffs, long nseq);
+int xgpr_conv_grad_rows_f32(const float *x, float *zrows, float *grows, const int8_t *radem, const float *chi,
+                            const int32_t *seqlen_host, const int32_t *seqlen_dev,
+                            long n, long L, long C, long num_rffs, long num_freqs, long radem_shape2,
+                            long nseq, double sigma, int conv_width, int scaling_type, int fit_intercept,
+                            void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- cudaConv1dMaxpool (xgpr_cuda_rfgen_cpp_ext.cpp:61-69): out[n, num_rffs] float32,
  * out = max(out, chi * sorf(window)) over k-mers; num_freqs == num_rffs;
  * radem_shape2 == reps * P exactly (conv1d_operations.cpp:65-68). */

@@ -31,6 +31,7 @@ SIGNATURES = {
     "xgpr_conv1d_fgen_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _l, _l, _l, _l, _l, _l, _l, _l, _i, _i, _vp, _sz, _vp],
     "xgpr_conv1d_fgen_f64": [_vp, _vp, _vp, _vp, _vp, _vp, _l, _l, _l, _l, _l, _l, _l, _l, _i, _i, _vp, _sz, _vp],
     "xgpr_conv_feature_rows_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _l, _l, _l, _l, _l, _l, _l, _i, _i, _i, _vp, _sz, _vp],
+    "xgpr_conv_grad_rows_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _l, _l, _l, _l, _l, _l, _l, _d, _i, _i, _i, _vp, _sz, _vp],
     "xgpr_conv_grad_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _l, _l, _l, _l, _l, _l, _l, _l, _l, _l, _d, _i, _i,
                            _vp, _sz, _vp],
     "xgpr_conv_grad_f64": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _l, _l, _l, _l, _l, _l, _l, _l, _l, _l, _d, _i, _i,
@@ -71,6 +72,7 @@ SIZE_FUNCS = {
     "xgpr_sorf_workspace_bytes": [_l, _l, _i],
     "xgpr_conv_workspace_bytes": [_l, _l, _i, _l],
     "xgpr_conv_feature_rows_workspace_bytes": [_l, _l, _l, _l],
+    "xgpr_conv_grad_rows_workspace_bytes": [_l, _l, _l, _l],
     "xgpr_precond_apply_workspace_bytes": [_l],
     "xgpr_precond_utr_block_workspace_bytes": [_l, _l, _l],
     "xgpr_precond_apply_block_workspace_bytes": [_l, _l, _l],

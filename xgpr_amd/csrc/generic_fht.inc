@@ -122,7 +122,10 @@ __global__ void global_stage_kernel(T *x, long npairs, long h) {
 // MODE_CONV_ROWS: the float32 feature rows of the sequence kernels (xgpr_conv_feature_rows_f32) on the wave tiles of wave_tile.inc --
 // MODE_CONV's sums started from zero, rounded once and stored as float32.  This kernel does not take the mode: it keeps its sums in the
 // float64 output between k-mers, so the any-width windows stage MODE_CONV through a float64 slice and round (launchers.inc).
-enum { MODE_RBF = 0, MODE_RBF_GRAD = 1, MODE_CONV = 2, MODE_CONV_GRAD = 3, MODE_MAXPOOL = 4, MODE_RBF_CACHE = 5, MODE_CONV_ROWS = 6 };
+// MODE_CONV_GRAD_ROWS: the float32 feature and gradient rows of the sequence kernels (xgpr_conv_grad_rows_f32), MODE_CONV_GRAD's sums
+// rounded once into outf / gradf -- on the wave tiles only, as MODE_CONV_ROWS; the any-width windows stage MODE_CONV_GRAD and round.
+enum { MODE_RBF = 0, MODE_RBF_GRAD = 1, MODE_CONV = 2, MODE_CONV_GRAD = 3, MODE_MAXPOOL = 4, MODE_RBF_CACHE = 5, MODE_CONV_ROWS = 6,
+       MODE_CONV_GRAD_ROWS = 7 };
 
 template <typename T> struct SorfArgs {
     const T *x; double *out; double *grad; float *outf;
@@ -133,9 +136,9 @@ template <typename T> struct SorfArgs {
     int conv_width; int P; int reps; int scaling_type;
     T nc; double scale; double sigma;
     T *scratch;       // GLOBALBUF only: one P-element buffer per workgroup, in global memory
-    int fit_intercept;   // MODE_CONV_ROWS only: column 0 of every row is 1.0f
+    int fit_intercept;   // the float32 row modes only: column 0 of every row is 1.0f (0.0f in the gradient rows)
     int grad_split;      // wave_tile_rbf_kernel<.., GRAD>: grad is only 8-byte aligned, its (-sin, cos) pairs go out as two 8-byte stores
-    float *gradf;        // wave_tile_rbf_grad_rows_kernel: the float32 gradient rows (the feature rows go to outf)
+    float *gradf;        // wave_tile_rbf_grad_rows_kernel, MODE_CONV_GRAD_ROWS: the float32 gradient rows (the feature rows go to outf)
 };
 
 // one workgroup per (datapoint i = blockIdx.x, repeat k = blockIdx.y); for the conv ops the

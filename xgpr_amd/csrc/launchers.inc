@@ -355,12 +355,36 @@ int conv_rows_staged(const float *x, float *zc, const int8_t *radem, const float
                      const int32_t *seqlen_dev, long n, long L, long C, long num_rffs, long num_freqs, long R, int conv_width,
                      int scaling_type, int fit_intercept, void *workspace, size_t wbytes, hipStream_t st);
 
+// ---- float32 feature AND gradient rows of the sequence kernels (xgpr_conv_grad_rows_f32, mode MODE_CONV_GRAD_ROWS of conv_impl): outf =
+// zrows[n, num_rffs], gradf = grows[n, num_rffs].  The dispatch of the feature rows above with the gradient operator's kernels: windows up
+// to 1024 elements wave_conv_kernel<LG, CONV_GRAD_ROWS>, 2048 / 4096 wave_tile_conv_kernel<float, LG, MODE_CONV_GRAD_ROWS>, every other
+// shape the float64 gradient operator slice by slice into TWO float64 staging arrays (out, grad) behind the operator's own workspace --
+// together within CONV_ROWS_STAGE_BYTES -- and one rounding pass each.
+size_t conv_grad_rows_workspace_bytes(long R, long width, long num_rffs, long nseq) {
+    const long P = padded_width(width);
+    size_t b = conv_rows_stage_offset(R, P, nseq);
+    if (P > 1024 && nseq > 0 && num_rffs > 0) {
+        const size_t row = (size_t)num_rffs * sizeof(double), half = CONV_ROWS_STAGE_BYTES / 2;
+        size_t rows = half / row > 0 ? half / row : 1;
+        if (rows > (size_t)nseq) rows = (size_t)nseq;
+        b += 2 * align_up(rows * row, 256);
+    }
+    return b;
+}
+
+int conv_grad_rows_staged(const float *x, float *zrows, float *grows, const int8_t *radem, const float *chi, const int32_t *seqlen_host,
+                          const int32_t *seqlen_dev, long n, long L, long C, long num_rffs, long num_freqs, long R, double sigma,
+                          int conv_width, int scaling_type, int fit_intercept, void *workspace, size_t wbytes, hipStream_t st);
+
 template <typename T>
 int conv_impl(const T *x, double *out, double *grad, float *outf, const int8_t *radem, const T *chi,
               const int32_t *seqlen_host, const int32_t *seqlen_dev, long n, long L, long C, long out_rows,
               long num_rffs, long grad_rows, long grad_cols, long num_freqs, long R, long nseq, double sigma,
-              int conv_width, int scaling_type, int mode, void *workspace, size_t wbytes, void *stream, int fit_intercept = 0) {
-    if (mode == MODE_CONV_ROWS && sizeof(T) != 4) return fail(XGPR_ERR_UNSUPPORTED, "float32 feature rows take float32 input");
+              int conv_width, int scaling_type, int mode, void *workspace, size_t wbytes, void *stream, int fit_intercept = 0,
+              float *gradf = nullptr) {
+    const bool rows_mode = mode == MODE_CONV_ROWS || mode == MODE_CONV_GRAD_ROWS;      // float32 rows out: no float64 output to check
+    const bool grad_mode = mode == MODE_CONV_GRAD || mode == MODE_CONV_GRAD_ROWS;
+    if (rows_mode && sizeof(T) != 4) return fail(XGPR_ERR_UNSUPPORTED, "float32 feature rows take float32 input");
     if (n == 0 || out_rows != n) return fail(XGPR_ERR_NO_DATAPOINTS, "no datapoints");
     if (num_rffs < 2 || (num_rffs & 1) != 0) return fail(XGPR_ERR_ODD_OUTPUT, "last dim of output must be even number");
     if (mode == MODE_MAXPOOL) {
@@ -381,12 +405,14 @@ int conv_impl(const T *x, double *out, double *grad, float *outf, const int8_t *
     if (rc) return rc;
     if (!seqlen_dev) return fail(XGPR_ERR_WORKSPACE, "seqlen_dev (device copy of the sequence lengths) is required");
     hipStream_t st = (hipStream_t)stream;
-    if (mode == MODE_CONV_ROWS && (!outf || (reinterpret_cast<uintptr_t>(outf) & 7) != 0))
+    if (rows_mode && (!outf || (reinterpret_cast<uintptr_t>(outf) & 7) != 0))
         return fail(XGPR_ERR_WORKSPACE, "feature rows pointer must be 8-byte aligned");
+    if (mode == MODE_CONV_GRAD_ROWS && (!gradf || (reinterpret_cast<uintptr_t>(gradf) & 7) != 0))
+        return fail(XGPR_ERR_WORKSPACE, "gradient rows pointer must be 8-byte aligned");
 
     if constexpr (sizeof(T) == 4) {
         if (P <= 1024) {
-            if (mode != MODE_MAXPOOL && mode != MODE_CONV_ROWS && !aligned16(out)) return fail(XGPR_ERR_WORKSPACE, "output pointer must be 16-byte aligned");
+            if (mode != MODE_MAXPOOL && !rows_mode && !aligned16(out)) return fail(XGPR_ERR_WORKSPACE, "output pointer must be 16-byte aligned");
             if (mode == MODE_CONV_GRAD && !aligned16(grad)) return fail(XGPR_ERR_WORKSPACE, "gradient pointer must be 16-byte aligned");
             if (!workspace || wbytes < masks_bytes(R)) return fail(XGPR_ERR_WORKSPACE, "workspace too small (see xgpr_rbf_workspace_bytes)");
             WaveArgs a = {};
@@ -395,7 +421,7 @@ int conv_impl(const T *x, double *out, double *grad, float *outf, const int8_t *
             a.conv_width = conv_width; a.scaling_type = scaling_type; a.fit_intercept = fit_intercept;
             a.MW = masks_per_diag(R); a.nb = (int)((num_freqs + 1023) / 1024);
             a.scale = sqrt(1.0 / (double)num_freqs);
-            if (mode == MODE_CONV_GRAD) { a.grad = grad; a.sigma = sigma; }
+            if (grad_mode) { a.grad = grad; a.gradf = gradf; a.sigma = sigma; }
             const int lg = ilog2(P);
             fill_norms(a, lg);
             rc = pack_masks(radem, (uint64_t *)workspace, R, a.MW, st);
@@ -416,6 +442,10 @@ int conv_impl(const T *x, double *out, double *grad, float *outf, const int8_t *
 #define CALL_CONV_G(LG) CALL_CONV(LG, CONV_GRAD)
                 DISPATCH_LOG2P(lg, CALL_CONV_G)
 #undef CALL_CONV_G
+            } else if (mode == MODE_CONV_GRAD_ROWS) {
+#define CALL_CONV_GR(LG) CALL_CONV(LG, CONV_GRAD_ROWS)
+                DISPATCH_LOG2P(lg, CALL_CONV_GR)
+#undef CALL_CONV_GR
             } else if (mode == MODE_CONV_ROWS) {
 #define CALL_CONV_R(LG) CALL_CONV(LG, CONV_ROWS)
                 DISPATCH_LOG2P(lg, CALL_CONV_R)
@@ -435,7 +465,7 @@ int conv_impl(const T *x, double *out, double *grad, float *outf, const int8_t *
         }
     }
     SorfArgs<T> a = {};
-    a.x = x; a.out = out; a.grad = grad; a.outf = outf; a.radem = radem; a.chi = chi; a.seqlen = seqlen_dev;
+    a.x = x; a.out = out; a.grad = grad; a.outf = outf; a.gradf = gradf; a.radem = radem; a.chi = chi; a.seqlen = seqlen_dev;
     a.n = n; a.row_stride = L * C; a.F = num_freqs; a.R = R; a.d = (int)win; a.kmer_stride = (int)C;
     a.conv_width = conv_width; a.P = (int)P; a.reps = reps; a.scaling_type = scaling_type;
     a.nc = norm_constant<T>(P); a.scale = sqrt(1.0 / (double)num_freqs); a.sigma = sigma; a.fit_intercept = fit_intercept;
@@ -444,13 +474,14 @@ int conv_impl(const T *x, double *out, double *grad, float *outf, const int8_t *
         // 2048 / 4096 (narrower float32 windows were served above); XGPR_F64_PLAN=generic keeps the any-width path (A/B)
         const bool generic64 = wave_tile_plan_off();
         const bool mine = sizeof(T) == 8 ? P <= 4096 : (P > 1024 && P <= 4096);      // (8 / 16 waves per transform leave too few registers for the accumulators)
-        const bool aligned = mode == MODE_MAXPOOL || mode == MODE_CONV_ROWS || (aligned16(out) && (mode != MODE_CONV_GRAD || aligned16(grad)));
+        const bool aligned = mode == MODE_MAXPOOL || rows_mode || (aligned16(out) && (mode != MODE_CONV_GRAD || aligned16(grad)));
         if (mine && !generic64 && aligned && R % 64 == 0 && (reinterpret_cast<uintptr_t>(radem) & 15) == 0) {
             const long items = n * (P > 1024 ? R / 1024 : (num_freqs + 1023) / 1024);
 #define CALL_CONVT(LG) if constexpr ((sizeof(T) == 8 || LG > 10) && LG <= 12) { \
                 using WT = WaveTile<T, LG>; \
                 if (mode == MODE_CONV) return launch_wave_tile(wave_tile_conv_kernel<T, LG, MODE_CONV>, a, items, WT::WAVES, WT::LDS_BYTES, st, "wave_tile_conv_kernel launch"); \
                 if constexpr (sizeof(T) == 4) { if (mode == MODE_CONV_ROWS) return launch_wave_tile(wave_tile_conv_kernel<T, LG, MODE_CONV_ROWS>, a, items, WT::WAVES, WT::LDS_BYTES, st, "wave_tile_conv_kernel launch"); } \
+                if constexpr (sizeof(T) == 4) { if (mode == MODE_CONV_GRAD_ROWS) return launch_wave_tile(wave_tile_conv_kernel<T, LG, MODE_CONV_GRAD_ROWS>, a, items, WT::WAVES, WT::LDS_BYTES, st, "wave_tile_conv_kernel launch"); } \
                 if (mode == MODE_CONV_GRAD) return launch_wave_tile(wave_tile_conv_kernel<T, LG, MODE_CONV_GRAD>, a, items, WT::WAVES, WT::LDS_BYTES, st, "wave_tile_conv_kernel launch"); \
                 return launch_wave_tile(wave_tile_conv_kernel<T, LG, MODE_MAXPOOL>, a, items, WT::WAVES, WT::LDS_BYTES, st, "wave_tile_conv_kernel launch"); }
             DISPATCH_LOG2P_WT(ilog2(P), CALL_CONVT)
@@ -461,6 +492,12 @@ int conv_impl(const T *x, double *out, double *grad, float *outf, const int8_t *
         if constexpr (sizeof(T) == 4)
             return conv_rows_staged(x, outf, radem, chi, seqlen_host, seqlen_dev, n, L, C, num_rffs, num_freqs, R, conv_width, scaling_type,
                                     fit_intercept, workspace, wbytes, st);
+        else return fail(XGPR_ERR_UNSUPPORTED, "float32 feature rows take float32 input");
+    }
+    if (mode == MODE_CONV_GRAD_ROWS) {
+        if constexpr (sizeof(T) == 4)
+            return conv_grad_rows_staged(x, outf, gradf, radem, chi, seqlen_host, seqlen_dev, n, L, C, num_rffs, num_freqs, R, sigma, conv_width,
+                                         scaling_type, fit_intercept, workspace, wbytes, st);
         else return fail(XGPR_ERR_UNSUPPORTED, "float32 feature rows take float32 input");
     }
     if (mode == MODE_CONV) return launch_generic_sorf<T, MODE_CONV>(a, workspace, wbytes, st);
@@ -489,6 +526,43 @@ int conv_rows_staged(const float *x, float *zc, const int8_t *radem, const float
         if (nblocks > 2147483647L) return fail(XGPR_ERR_UNSUPPORTED, "staging slice too large for one rounding launch");
         hipLaunchKernelGGL(round_rows_kernel, dim3((unsigned)nblocks), dim3(256), 0, st, reinterpret_cast<const double2 *>(stage),
                            reinterpret_cast<float2 *>(zc + lo * num_rffs), npairs, num_rffs / 2, fit_intercept);
+        HIP_TRY(hipGetLastError(), "round_rows_kernel launch");
+    }
+    return 0;
+}
+
+int conv_grad_rows_staged(const float *x, float *zrows, float *grows, const int8_t *radem, const float *chi, const int32_t *seqlen_host,
+                          const int32_t *seqlen_dev, long n, long L, long C, long num_rffs, long num_freqs, long R, double sigma,
+                          int conv_width, int scaling_type, int fit_intercept, void *workspace, size_t wbytes, hipStream_t st) {
+    const long P = padded_width((long)conv_width * C);
+    const size_t off = conv_rows_stage_offset(R, P, n), row = (size_t)num_rffs * sizeof(double);
+    // two arrays of `half` bytes each (a multiple of 256: both 16-byte aligned, as the float64 operator's double2 accesses need)
+    const size_t half = (!workspace || wbytes < off) ? 0 : (wbytes - off) / 2 / 256 * 256;
+    if (!workspace || !aligned16(workspace) || half < row)
+        return fail(XGPR_ERR_WORKSPACE, "workspace too small (see xgpr_conv_grad_rows_workspace_bytes)");
+    double *stage_z = reinterpret_cast<double *>(reinterpret_cast<unsigned char *>(workspace) + off);
+    double *stage_g = reinterpret_cast<double *>(reinterpret_cast<unsigned char *>(workspace) + off + half);
+    long rows = (long)(half / row);
+    if (rows > n) rows = n;
+    for (long lo = 0; lo < n; lo += rows) {
+        const long cnt = n - lo < rows ? n - lo : rows;
+        HIP_TRY(hipMemsetAsync(stage_z, 0, (size_t)cnt * row, st), "hipMemsetAsync (gradient rows staging)");
+        HIP_TRY(hipMemsetAsync(stage_g, 0, (size_t)cnt * row, st), "hipMemsetAsync (gradient rows staging)");
+        int rc = conv_impl<float>(x + lo * L * C, stage_z, stage_g, nullptr, radem, chi, seqlen_host + lo, seqlen_dev + lo, cnt, L, C, cnt,
+                                  num_rffs, cnt, num_rffs, num_freqs, R, cnt, sigma, conv_width, scaling_type, MODE_CONV_GRAD, workspace, off,
+                                  (void *)st);
+        if (rc) return rc;
+        // KernelBase.gradient_x: xgrad[:, 0] = 0 under an intercept (the rounding pass below writes the 1.0f of the features itself)
+        if (fit_intercept)
+            HIP_TRY(hipMemset2DAsync(stage_g, row, 0, sizeof(double), (size_t)cnt, st), "hipMemset2DAsync (gradient rows staging)");
+        const long npairs = cnt * (num_rffs / 2);
+        const long nblocks = (npairs + 255) / 256;
+        if (nblocks > 2147483647L) return fail(XGPR_ERR_UNSUPPORTED, "staging slice too large for one rounding launch");
+        hipLaunchKernelGGL(round_rows_kernel, dim3((unsigned)nblocks), dim3(256), 0, st, reinterpret_cast<const double2 *>(stage_z),
+                           reinterpret_cast<float2 *>(zrows + lo * num_rffs), npairs, num_rffs / 2, fit_intercept);
+        HIP_TRY(hipGetLastError(), "round_rows_kernel launch");
+        hipLaunchKernelGGL(round_rows_kernel, dim3((unsigned)nblocks), dim3(256), 0, st, reinterpret_cast<const double2 *>(stage_g),
+                           reinterpret_cast<float2 *>(grows + lo * num_rffs), npairs, num_rffs / 2, 0);
         HIP_TRY(hipGetLastError(), "round_rows_kernel launch");
     }
     return 0;

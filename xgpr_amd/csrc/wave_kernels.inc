@@ -153,8 +153,13 @@ __global__ __launch_bounds__(1024) void conv_order_kernel(const int32_t *__restr
 // LDS, laundered sign words, prefetch of the next window, float64 sums in the same order); the epilogue OVERWRITES
 // a.outf[i, 2 f ..] with (float)(0.0 + sum * rs) as (cos, sin) float2 pairs -- what CONV_FGEN leaves in a zeroed float64
 // output, rounded once -- and puts 1.0f into column 0 under fit_intercept.  No load of the old value.
-enum { CONV_FGEN = 0, CONV_MAXPOOL = 1, CONV_GRAD = 2, CONV_ROWS = 3 };
+// MODE 4 = the float32 feature AND gradient rows (xgpr_conv_grad_rows_f32): CONV_GRAD's front end and k-mer loop unchanged (the
+// per-k-mer roundings to float, the four float64 sums in the same order); the epilogue OVERWRITES a.outf[i, 2 f ..] and
+// a.gradf[i, 2 f ..] with (float)(0.0 + sum) as float2 pairs -- what CONV_GRAD leaves in zeroed float64 out / grad, rounded
+// once -- and puts 1.0f / 0.0f into column 0 under fit_intercept (KernelBase.gradient_x).  No load of the old values.
+enum { CONV_FGEN = 0, CONV_MAXPOOL = 1, CONV_GRAD = 2, CONV_ROWS = 3, CONV_GRAD_ROWS = 4 };
 constexpr bool conv_is_feat(int mode) { return mode == CONV_FGEN || mode == CONV_ROWS; }
+constexpr bool conv_is_grad(int mode) { return mode == CONV_GRAD || mode == CONV_GRAD_ROWS; }
 #ifdef XGPR_ABL_NOC2
 #define XGPR_CONV_C2_ALL 0
 #else
@@ -162,7 +167,7 @@ constexpr bool conv_is_feat(int mode) { return mode == CONV_FGEN || mode == CONV
 #endif
 
 template <int LOG2P, int MODE>
-__global__ __launch_bounds__(256, (MODE == CONV_GRAD && LOG2P >= 7) ? 1 : (conv_is_feat(MODE) && (LOG2P >= 7 || XGPR_CONV_C2_ALL)) ? 3 : 2) void wave_conv_kernel(WaveArgs a) {
+__global__ __launch_bounds__(256, (conv_is_grad(MODE) && LOG2P >= 7) ? 1 : (conv_is_feat(MODE) && (LOG2P >= 7 || XGPR_CONV_C2_ALL)) ? 3 : 2) void wave_conv_kernel(WaveArgs a) {
     constexpr bool MAXPOOL = MODE == CONV_MAXPOOL;
     const int lane = threadIdx.x & 63;
     const long item = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) + (long)blockIdx.x * 4;
@@ -248,7 +253,7 @@ __global__ __launch_bounds__(256, (MODE == CONV_GRAD && LOG2P >= 7) ? 1 : (conv_
             const long f = fe0 + r * FE_STEP;
             if (f < a.F) orow[f] = acc[r];
         }
-    } else if constexpr (MODE == CONV_GRAD) {
+    } else if constexpr (conv_is_grad(MODE)) {
         // cudaConvGrad: per k-mer the roundings of shared_rfgen_ops.cpp:140-155 (values rounded back
         // to float before they are accumulated), sums over k-mers in float64 in the reference's order
         double rs = a.scale;
@@ -275,16 +280,33 @@ __global__ __launch_bounds__(256, (MODE == CONV_GRAD && LOG2P >= 7) ? 1 : (conv_
                 gs[r] += cos_val * gv[r];
             }
         }
-        double *orow = a.out + i * 2 * a.F, *grow = a.grad + i * 2 * a.F;
-        #pragma unroll
-        for (int r = 0; r < 16; r++) {
-            const long f = fe0 + r * FE_STEP;
-            if (f < a.F) {
-                double2 *o = reinterpret_cast<double2 *>(orow + 2 * f), *g = reinterpret_cast<double2 *>(grow + 2 * f);
-                double2 ov = *o, gvv = *g;
-                ov.x += oc[r]; ov.y += os[r];
-                gvv.x += gc[r]; gvv.y += gs[r];
-                *o = ov; *g = gvv;
+        if constexpr (MODE == CONV_GRAD_ROWS) {
+            // (store patterns per layout: see CONV_ROWS below -- the same addresses, in two row arrays)
+            float *zrow = a.outf + i * 2 * a.F, *grow = a.gradf + i * 2 * a.F;
+            const bool icpt = a.fit_intercept != 0;
+            #pragma unroll
+            for (int r = 0; r < 16; r++) {
+                const long f = fe0 + r * FE_STEP;
+                if (f < a.F) {
+                    const bool c0 = icpt && f == 0;                 // KernelBase.gradient_x: xtrans[:, 0] = 1, xgrad[:, 0] = 0
+                    const float zc = (float)(0.0 + oc[r]), zs = (float)(0.0 + os[r]);      // (0.0 + x: the sibling's `old + x` on zeroed outputs)
+                    const float dc = (float)(0.0 + gc[r]), ds = (float)(0.0 + gs[r]);
+                    *reinterpret_cast<float2 *>(zrow + 2 * f) = make_float2(c0 ? 1.0f : zc, zs);
+                    *reinterpret_cast<float2 *>(grow + 2 * f) = make_float2(c0 ? 0.0f : dc, ds);
+                }
+            }
+        } else {
+            double *orow = a.out + i * 2 * a.F, *grow = a.grad + i * 2 * a.F;
+            #pragma unroll
+            for (int r = 0; r < 16; r++) {
+                const long f = fe0 + r * FE_STEP;
+                if (f < a.F) {
+                    double2 *o = reinterpret_cast<double2 *>(orow + 2 * f), *g = reinterpret_cast<double2 *>(grow + 2 * f);
+                    double2 ov = *o, gvv = *g;
+                    ov.x += oc[r]; ov.y += os[r];
+                    gvv.x += gc[r]; gvv.y += gs[r];
+                    *o = ov; *g = gvv;
+                }
             }
         }
     } else {

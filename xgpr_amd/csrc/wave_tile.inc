@@ -362,10 +362,14 @@ __global__ __launch_bounds__(wt_waves(LOG2P) * 64) void wave_tile_rbf_grad_rows_
 // MODE_CONV_ROWS (T = float, windows of 2048 / 4096 elements: xgpr_conv_feature_rows_f32): MODE_CONV with the sums started from 0.0 instead
 // of a load of the zeroed output, rounded once to float32 and stored as (cos, sin) float2 pairs into a.outf[i, 2 f ..] -- layout C, one
 // store instruction writes 64 consecutive pairs (512 bytes); column 0 is 1.0f under fit_intercept.
+// MODE_CONV_GRAD_ROWS (T = float, the same windows: xgpr_conv_grad_rows_f32): MODE_CONV_GRAD with its four sums started from 0.0, rounded
+// once and stored the same way into a.outf (features) and a.gradf (d features / d sigma); column 0 is 1.0f / 0.0f under fit_intercept.
 template <typename T, int LOG2P, int MODE>
 __global__ __launch_bounds__(wt_waves(LOG2P) * 64) void wave_tile_conv_kernel(SorfArgs<T> a) {
     using WT = WaveTile<T, LOG2P>;
-    static_assert(MODE == MODE_CONV || MODE == MODE_CONV_GRAD || MODE == MODE_MAXPOOL || MODE == MODE_CONV_ROWS, "convolution modes");
+    static_assert(MODE == MODE_CONV || MODE == MODE_CONV_GRAD || MODE == MODE_MAXPOOL || MODE == MODE_CONV_ROWS || MODE == MODE_CONV_GRAD_ROWS,
+                  "convolution modes");
+    static_assert(MODE != MODE_CONV_GRAD_ROWS || sizeof(T) == 4, "the gradient rows take float32 input");
     constexpr bool FEAT = MODE == MODE_CONV || MODE == MODE_CONV_ROWS;
     extern __shared__ __attribute__((aligned(16))) unsigned char wt_lds[];
     T *tbuf = reinterpret_cast<T *>(wt_lds);
@@ -394,7 +398,7 @@ __global__ __launch_bounds__(wt_waves(LOG2P) * 64) void wave_tile_conv_kernel(So
     const WT wt(tbuf, wv, lane);
     int4 rw[3];
     wt.load_signs(rw, a.radem, a.R, b);
-    constexpr int NACC = FEAT ? 2 : (MODE == MODE_CONV_GRAD ? 4 : 0);
+    constexpr int NACC = FEAT ? 2 : ((MODE == MODE_CONV_GRAD || MODE == MODE_CONV_GRAD_ROWS) ? 4 : 0);
     double acc[NACC > 0 ? NACC : 1][16];
     float mx[16];
     double *orow = a.out + i * 2 * a.F, *grow = a.grad + i * 2 * a.F;
@@ -405,6 +409,7 @@ __global__ __launch_bounds__(wt_waves(LOG2P) * 64) void wave_tile_conv_kernel(So
         const bool in = f < a.F;
         if constexpr (MODE == MODE_MAXPOOL) mx[r] = in ? mrow[f] : 0.0f;
         else if constexpr (MODE == MODE_CONV_ROWS) { acc[0][r] = 0.0; acc[1][r] = 0.0; }
+        else if constexpr (MODE == MODE_CONV_GRAD_ROWS) { acc[0][r] = 0.0; acc[1][r] = 0.0; acc[2][r] = 0.0; acc[3][r] = 0.0; }
         else {
             const double2 o = in ? *reinterpret_cast<const double2 *>(orow + 2 * f) : make_double2(0.0, 0.0);
             acc[0][r] = o.x; acc[1][r] = o.y;
@@ -473,6 +478,10 @@ __global__ __launch_bounds__(wt_waves(LOG2P) * 64) void wave_tile_conv_kernel(So
             else if constexpr (MODE == MODE_CONV_ROWS) {
                 const float c = (a.fit_intercept && f == 0) ? 1.0f : (float)acc[0][r];
                 *reinterpret_cast<float2 *>(a.outf + i * 2 * a.F + 2 * f) = make_float2(c, (float)acc[1][r]);
+            } else if constexpr (MODE == MODE_CONV_GRAD_ROWS) {
+                const bool c0 = a.fit_intercept && f == 0;
+                *reinterpret_cast<float2 *>(a.outf + i * 2 * a.F + 2 * f) = make_float2(c0 ? 1.0f : (float)acc[0][r], (float)acc[1][r]);
+                *reinterpret_cast<float2 *>(a.gradf + i * 2 * a.F + 2 * f) = make_float2(c0 ? 0.0f : (float)acc[2][r], (float)acc[3][r]);
             } else {
                 *reinterpret_cast<double2 *>(orow + 2 * f) = make_double2(acc[0][r], acc[1][r]);
                 if constexpr (MODE == MODE_CONV_GRAD) *reinterpret_cast<double2 *>(grow + 2 * f) = make_double2(acc[2][r], acc[3][r]);

@@ -186,6 +186,17 @@ int xgpr_conv_grad_f32(const float *x, double *out, double *grad, const int8_t *
                             grad_rows, grad_cols, num_freqs, radem_shape2, nseq, sigma, conv_width, scaling_type,
                             MODE_CONV_GRAD, workspace, workspace_bytes, stream);
 }
+size_t xgpr_conv_grad_rows_workspace_bytes(long radem_shape2, long width, long num_rffs, long nseq) {
+    return conv_grad_rows_workspace_bytes(radem_shape2, width, num_rffs, nseq);
+}
+int xgpr_conv_grad_rows_f32(const float *x, float *zrows, float *grows, const int8_t *radem, const float *chi,
+                            const int32_t *seqlen_host, const int32_t *seqlen_dev, long n, long L, long C, long num_rffs,
+                            long num_freqs, long radem_shape2, long nseq, double sigma, int conv_width, int scaling_type,
+                            int fit_intercept, void *workspace, size_t workspace_bytes, void *stream) {
+    return conv_impl<float>(x, nullptr, nullptr, zrows, radem, chi, seqlen_host, seqlen_dev, n, L, C, n, num_rffs, 0, 0, num_freqs,
+                            radem_shape2, nseq, sigma, conv_width, scaling_type, MODE_CONV_GRAD_ROWS, workspace, workspace_bytes,
+                            stream, fit_intercept != 0, grows);
+}
 int xgpr_conv_grad_f64(const double *x, double *out, double *grad, const int8_t *radem, const double *chi,
                        const int32_t *seqlen_host, const int32_t *seqlen_dev, long n, long L, long C, long out_rows,
                        long num_rffs, long grad_rows, long grad_cols, long num_freqs, long radem_shape2, long nseq,

@@ -371,6 +371,20 @@ class ConvSORFKernel(KernelBase):
                                self._host_lengths(x_scaled, sequence_length), self.conv_width, self.scaling_type,
                                self.fit_intercept)
 
+    def grad_rows_ok(self):
+        """Whether ``fill_grad_rows`` can write this kernel's float32 feature AND gradient rows, and the exact NMLL
+        gradient's accumulations can run on them (nmll.calc_gradient_terms): a HIP device -- the writer serves every
+        window width the float64 gradient operator serves -- and whole 128 x 128 tiles for the two Gram kernels."""
+        return torch.device(self.device).type == "cuda" and ext.cross_gram_ok(self.num_rffs)
+
+    def fill_grad_rows(self, x_unscaled, zrows, grows, sequence_length):
+        """zrows, grows [w, M] float32 <- the complete feature rows and d(features)/d(sigma) rows of the UNSCALED float32
+        sequences: ``gradient_x`` rounded once to float32 (its entries are float64 sums over k-mers of float32 values),
+        intercept column included.  Both overwritten."""
+        ext.hipConvGradRows(x_unscaled, zrows, grows, self.radem_diag, self.chi_arr,
+                            self._host_lengths(x_unscaled, sequence_length), float(self.hyperparams[1]), self.conv_width,
+                            self.scaling_type, self.fit_intercept)
+
     def transform_x(self, input_x, sequence_length=None, rows_out=None, pre_scaled=False):
         """kernel_baseclass.py:269-299 -> float64 [n, M] as for every kernel.  With ``rows_out`` (float32 [n, M] on the
         device) the same features are written there as float32 rows by ``fill_feature_rows`` -- no float64 array is made --
@@ -593,6 +607,18 @@ class Conv1dTwoLayerKernel(KernelBase):
         ext.hipRBFGrad(featurized_x, output_x, dz_dsigma, self.radem_diag, self.chi_arr,
                        float(self.hyperparams[1]), self.fit_intercept)
         return output_x, dz_dsigma
+
+    def grad_rows_ok(self):
+        """As ``SORFKernel.grad_rows_ok`` for the second (RBF) layer, whose input is the ``init_rffs`` pooled features: a
+        HIP device, a padded width hipRBFGradRows has a plan for, whole 128 x 128 tiles for the two Gram kernels."""
+        return (torch.device(self.device).type == "cuda" and padded_dims(self.init_rffs) <= ext.GRAD_ROWS_MAX_WIDTH
+                and ext.cross_gram_ok(self.num_rffs) and self.radem_diag.data_ptr() % 16 == 0)
+
+    def fill_grad_rows(self, x_unscaled, zrows, grows, sequence_length):
+        """zrows, grows [w, M] float32 <- ``gradient_x`` of the UNSCALED float32 sequences, exactly: the gradient is
+        hipRBFGrad over the max-pooled float32 first-layer features, every entry of which is a float32 value."""
+        ext.hipRBFGradRows(self._first_layer(x_unscaled, sequence_length), zrows, grows, self.radem_diag, self.chi_arr,
+                           float(self.hyperparams[1]), self.fit_intercept)
 
     # the resident float32 cache holds complete feature rows, as for the other sequence kernels
     def cache_ok(self):

@@ -2,10 +2,11 @@
 quadrature) form that drives hyperparameter tuning -- the "next" rows 1 and 2 of SURVEY.md
 section 8f.  They reuse the hot path unchanged: the approximate NMLL is one preconditioned CG solve
 with k = nsamples + 1 = 26 right-hand sides, whose block matvec runs on the float64 matrix cores
-(hipZCacheBlockMatvec); the gradient terms of the fixed-vector kernels are accumulated from float32
-feature and gradient rows (hipRBFGradRows) by the two Gram kernels on the same matrix cores
-(hipZtZGram, hipCrossGram), those of the other kernels are the gradient operators (hipConvGrad,
-hipMiniARDGrad, ...) followed by dense M x M accumulations.
+(hipZCacheBlockMatvec); the gradient terms of every kernel with a single lengthscale -- the fixed-vector
+kernels, the sequence and graph kernels, the two-layer kernel -- are accumulated from float32 feature and
+gradient rows (hipRBFGradRows, hipConvGradRows) by the two Gram kernels on the same matrix cores
+(hipZtZGram, hipCrossGram), those of the other kernels (MiniARD, Linear) are the float64 gradient
+operators (hipMiniARDGrad, ...) followed by dense M x M accumulations.
 
   * ``optimize_alpha_beta``     <-> scoring_toolkit/alpha_beta_optimizer.py:13-39
   * ``generate_normal_probes``  <-> scoring_toolkit/probe_generators.py:9-30 (gpu) / :54-75 (cpu)
@@ -25,7 +26,7 @@ import numpy as np
 import torch
 from scipy.linalg import eigh_tridiagonal
 
-from .cg import ConjugateGrad, _resolve_cache_mode
+from .cg import ConjugateGrad, _resolve_cache_mode, window_ranges
 from .exact import calc_design_mat, direct_weight_calc
 from .preconditioner import RandNysPreconditioner
 
@@ -134,15 +135,24 @@ def _check_subsample(subsample):
 
 
 def _grad_rows_route(dataset, kernel):
-    """Whether the gradient terms are accumulated from float32 feature and gradient rows: the fixed-vector kernels on a
-    HIP device wherever ``SORFKernel.grad_rows_ok``, over a shard the writer can read as it is (float32, 2-d, on the
-    device; anything else goes through the float64 formulation, which converts each chunk)."""
+    """Whether the gradient terms are accumulated from float32 feature and gradient rows: the kernels with a single
+    lengthscale on a HIP device wherever their ``grad_rows_ok`` holds, over a shard the writer can read as it is (float32,
+    contiguous, on the device: 2-d for the fixed-vector kernels, 3-d with its sequence lengths for the sequence, graph
+    and two-layer kernels; anything else goes through the float64 formulation, which converts each chunk)."""
     fn = getattr(kernel, "grad_rows_ok", None)
     if fn is None or not hasattr(dataset, "get_xdata") or not fn():
         return False
     xall = dataset.get_xdata()
-    return (isinstance(xall, torch.Tensor) and xall.is_cuda and xall.dtype == torch.float32 and xall.dim() == 2
-            and xall.is_contiguous())
+    if not (isinstance(xall, torch.Tensor) and xall.is_cuda and xall.dtype == torch.float32 and xall.is_contiguous()):
+        return False
+    if xall.dim() == 3:
+        return _seq_grad_kernel(kernel) and dataset.get_sequence_lengths() is not None
+    return xall.dim() == 2 and not _seq_grad_kernel(kernel)
+
+
+def _seq_grad_kernel(kernel):
+    """Kernels over [n, L, C] sequences (three-dimensional ``xdim``): their ``fill_grad_rows`` takes the lengths."""
+    return len(getattr(kernel, "_xdim", ())) == 3
 
 
 def _grad_window_rows(m):
@@ -164,16 +174,19 @@ def _gradient_terms_rows(dataset, kernel, z_trans_z, z_trans_y, dz_dsigma_ty, in
     if n == 0:
         return
     yall = dataset.normalized_y()
+    lens = dataset.get_sequence_lengths() if _seq_grad_kernel(kernel) else None
     step = min(_grad_window_rows(m), n)
     dev = z_trans_z.device
     zwin = torch.empty((step, m), dtype=torch.float32, device=dev)
     gwin = torch.empty((step, m), dtype=torch.float32, device=dev)
     gws = cws = bws = None
     inner = inner_deriv[:, :, 0]
-    for lo in range(0, n, step):
-        hi = min(n, lo + step)
+    for lo, hi, wlens in window_ranges(n, step, lens):
         zr, gr = zwin[:hi - lo], gwin[:hi - lo]
-        kernel.fill_grad_rows(xall[lo:hi], zr, gr)
+        if lens is None:
+            kernel.fill_grad_rows(xall[lo:hi], zr, gr)
+        else:
+            kernel.fill_grad_rows(xall[lo:hi], zr, gr, wlens)
         yw = yall[lo:hi]
         ycol = yw.reshape(-1, 1).contiguous()
         need = ext.zcache_block_workspace_bytes(hi - lo, m, 1)
@@ -191,9 +204,10 @@ def calc_gradient_terms(dataset, kernel, subsample=1):
     of every chunk's rows that is used, drawn as the reference draws it (one generator seeded with 123, one
     ``choice`` without replacement per chunk, in chunk order); the last value returned is the number of rows used.
 
-    The fixed-vector kernels on a HIP device (``SORFKernel.grad_rows_ok``) accumulate all terms from float32 feature
-    and gradient rows (``_gradient_terms_rows``); everything else -- sequence kernels, MiniARD, two-layer, linear, CPU
-    tensors, feature counts that are not a multiple of 128, padded widths beyond 8192, and every subsampled
+    Every kernel with a single lengthscale on a HIP device -- fixed-vector (``SORFKernel.grad_rows_ok``), sequence and
+    graph (``ConvSORFKernel.grad_rows_ok``), two-layer -- accumulates all terms from float32 feature and gradient rows
+    (``_gradient_terms_rows``); everything else -- MiniARD, linear, CPU tensors, float64 or non-resident shards,
+    feature counts that are not a multiple of 128, fixed-vector padded widths beyond 8192, and every subsampled
     evaluation -- keeps the chunked float64 formulation."""
     _check_subsample(subsample)
     comm = dataset.comm

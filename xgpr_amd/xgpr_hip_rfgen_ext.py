@@ -442,6 +442,35 @@ def hipConvGrad(inputArr, outputArr, radem, chiArr, seqlengths, gradArr, sigma, 
         int(scalingType), wp, wn, _stream()))
 
 
+@_array_args("inputArr", "zRows", "gRows", "radem", "chiArr")
+def hipConvGradRows(inputArr, zRows, gRows, radem, chiArr, seqlengths, sigma, convWidth, scalingType, fitIntercept):
+    """cudaConvGrad writing float32 rows (xgpr_conv_grad_rows_f32): ``zRows[N, M]`` and ``gRows[N, M]`` (float32, 8-byte
+    aligned, rows of M contiguous floats; both OVERWRITTEN) hold what hipConvGrad adds into zeroed ``outputArr`` and
+    ``gradArr[:, :, 0]``, rounded once to float32, with column 0 set to 1 / 0 under fitIntercept: complete rows.  Argument
+    checks as hipConvGrad; float32 input only."""
+    x = _dev(inputArr, "inputArr", torch.float32, 3)
+    r = _radem3(radem)
+    c = _dev(chiArr, "chiArr", torch.float32, 1)
+    n = inputArr.shape[0]
+    for t, nm in ((zRows, "zRows"), (gRows, "gRows")):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or t.dim() != 2:
+            raise TypeError(f"{nm}: expected a 2-d float32 device tensor")
+        if t.shape[0] != n:
+            raise RuntimeError("no datapoints")
+        if t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) != t.shape[1]):
+            raise TypeError(f"{nm}: expected rows of M contiguous floats, M floats apart")
+    if tuple(gRows.shape) != tuple(zRows.shape):
+        raise RuntimeError("Wrong array sizes.")
+    host, dev = _seqlens(seqlengths, inputArr.device)
+    nbytes = _LIB.xgpr_conv_grad_rows_workspace_bytes(radem.shape[2], int(convWidth) * inputArr.shape[2], zRows.shape[1], n)
+    ws, wp, wn = _workspace(nbytes, inputArr.device)
+    return _lib.check(_LIB.xgpr_conv_grad_rows_f32(
+        x, C.c_void_p(zRows.data_ptr()), C.c_void_p(gRows.data_ptr()), r, c, C.c_void_p(host.ctypes.data),
+        C.c_void_p(dev.data_ptr()), n, inputArr.shape[1], inputArr.shape[2], zRows.shape[1], chiArr.shape[0],
+        radem.shape[2], host.shape[0], float(sigma), int(convWidth), int(scalingType), int(bool(fitIntercept)), wp, wn,
+        _stream()))
+
+
 @_array_args("inputArr", "outputArr", "radem", "chiArr")
 def hipConv1dMaxpool(inputArr, outputArr, radem, chiArr, seqlengths, convWidth):
     """cudaConv1dMaxpool (xgpr_cuda_rfgen_cpp_ext.cpp:61-69); float32 output."""
