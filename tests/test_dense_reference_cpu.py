@@ -27,6 +27,14 @@ SEQ = [(3, 12, 2, 1, 64), (4, 20, 16, 4, 300), (3, 23, 21, 9, 1000), (3, 30, 48,
        (2, 44, 100, 40, 4100), (2, 54, 100, 50, 8200)]
 GRAD_SEQ = [(4, 20, 16, 4, 300), (3, 30, 48, 21, 1030), (2, 44, 100, 40, 4100)]                     # 64, 1024, 4096
 TRANSFORM = [(3, 2), (3, 64), (2, 1024), (2, 2048), (2, 8192), (1, 16384)]                          # (rows, P) of the FHT / SRHT
+# One launch of every arm of the launchers' width dispatch (tests/test_gpu_dispatch_arms.py): each padded width 2^lg, lg = 1 .. 13, with
+# rows of exactly 2^lg numbers and of one fewer (16-byte-aligned rows and rows fetched float by float); three rows; 4096 features up to
+# 1024 (two tiles per row: the three-wave feature plan is reachable), one transform's worth beyond.  Sequences: conv_width 1, C = d,
+# L = 3, lengths 1, 2, 3 -- the window pads to 2^lg and the rows carry one, two and three k-mers.
+DISPATCH_LG = range(1, 14)
+DISPATCH_FIXED = [(3, d, 4096 if lg <= 10 else 2 << lg) for lg in DISPATCH_LG for d in (1 << lg, max(1, (1 << lg) - 1))]
+DISPATCH_SEQ = [(3, 3, d, 1, rffs) for _, d, rffs in DISPATCH_FIXED]
+DISPATCH_SEQLEN = (1, 2, 3)
 
 
 def _signs(rng, size):
@@ -58,13 +66,13 @@ class FixedCase:
 
 
 class SeqCase:
-    def __init__(self, n, L, C, cw, rffs):
+    def __init__(self, n, L, C, cw, rffs, seqlen=None):
         rng = np.random.default_rng([n, L, C, cw, rffs])
         self.n, self.L, self.C, self.cw, self.rffs, self.F = max(n, 3), L, C, cw, rffs, rffs // 2
         self.M = self.F + (self.F & 1)               # the max-pool operator wants an even number of outputs
         self.P = dr.padded_width(cw * C)
         self.x = (rng.standard_normal((self.n, L, C)) * (2.0 / np.sqrt(cw * C))).astype(np.float32)      # window norm ~ 2
-        self.seqlen = np.asarray([cw, L, min(L, cw + 2), (cw + L) // 2][:self.n], dtype=np.int32)
+        self.seqlen = np.asarray([cw, L, min(L, cw + 2), (cw + L) // 2][:self.n] if seqlen is None else seqlen, dtype=np.int32)
         self.radem = _signs(rng, (3, 1, ceil(self.M / self.P) * self.P))
         self.chi_all = np.sqrt(rng.chisquare(self.P, size=self.M)).astype(np.float32)
         self.chi = np.ascontiguousarray(self.chi_all[:self.F])
@@ -94,8 +102,8 @@ def fixed_case(n, d, rffs, scale):
 
 
 @functools.lru_cache(maxsize=None)
-def seq_case(n, L, C, cw, rffs):
-    return SeqCase(n, L, C, cw, rffs)
+def seq_case(n, L, C, cw, rffs, seqlen=None):
+    return SeqCase(n, L, C, cw, rffs, seqlen)
 
 
 def maxerr(got, ref):
@@ -248,6 +256,48 @@ def test_oracle_conv_grad(orc, n, L, C, cw, rffs, dtype):
         report(f"convgrad.f sc={scaling}", case, dtype, maxerr(of, rf), capf)
         report(f"convgrad.g sc={scaling}", case, dtype, maxerr(og, rg), capg)
         assert maxerr(of, rf) <= capf and maxerr(og, rg) <= capg
+
+
+# ---------------------------------------------------------------------------------------------------- the dispatch shapes
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+@pytest.mark.parametrize("icpt", [False, True])
+@pytest.mark.parametrize("n,d,rffs", DISPATCH_FIXED)
+def test_oracle_dispatch_shapes_fixed(orc, n, d, rffs, icpt, dtype):
+    case = fixed_case(n, d, rffs, GRAD_SCALE)
+    ref = dr.rbf_features(case.x, case.radem, case.chi, icpt, proj=case.proj)
+    err, cap = maxerr(oracle_rbf(orc, case, dtype, icpt), ref), dr.cap_rbf(dtype, case.x, case.chi, icpt)
+    report(f"rbf icpt={int(icpt)}", case, dtype, err, cap)
+    assert err <= cap
+    rf, rg = dr.rbf_grad(case.x, case.radem, case.chi, SIGMA, icpt, proj=case.proj)
+    of, og = oracle_rbf_grad(orc, case, dtype, icpt)
+    capf, capg = dr.cap_rbf_grad(dtype, case.x, case.chi, SIGMA, icpt, case.pmax)
+    report(f"rbfgrad.f i={int(icpt)}", case, dtype, maxerr(of, rf), capf)
+    report(f"rbfgrad.g i={int(icpt)}", case, dtype, maxerr(og, rg), capg)
+    assert maxerr(of, rf) <= capf and maxerr(og, rg) <= capg
+
+
+DISPATCH_SCALING = 1            # rows divided by sqrt(nkmers): the three k-mer counts give three row constants
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+@pytest.mark.parametrize("n,L,C,cw,rffs", DISPATCH_SEQ)
+def test_oracle_dispatch_shapes_sequences(orc, n, L, C, cw, rffs, dtype):
+    case = seq_case(n, L, C, cw, rffs, DISPATCH_SEQLEN)
+    sc = DISPATCH_SCALING
+    ref = dr.conv_features(case.x, case.seqlen, case.radem, case.chi, cw, sc, proj=case.proj)
+    err, cap = maxerr(oracle_conv(orc, case, dtype, sc), ref), dr.cap_conv(dtype, case.x, case.seqlen, case.chi, cw, sc)
+    report(f"conv sc={sc}", case, dtype, err, cap)
+    assert err <= cap
+    rf, rg = dr.conv_grad(case.x, case.seqlen, case.radem, case.chi, SIGMA, cw, sc, proj=case.proj)
+    of, og = oracle_conv_grad(orc, case, dtype, sc)
+    capf, capg = dr.cap_conv_grad(dtype, case.x, case.seqlen, case.chi, SIGMA, cw, sc, case.pmax)
+    report(f"convgrad.f sc={sc}", case, dtype, maxerr(of, rf), capf)
+    report(f"convgrad.g sc={sc}", case, dtype, maxerr(og, rg), capg)
+    assert maxerr(of, rf) <= capf and maxerr(og, rg) <= capg
+    _, ref = dr.conv_maxpool(case.x, case.seqlen, case.radem, case.chi_all, cw, proj=case.proj_all)
+    err, cap = maxerr(oracle_maxpool(orc, case, dtype), ref), dr.cap_conv_maxpool(dtype, case.x, case.seqlen, case.chi_all, cw, case.pmax)
+    report("maxpool", case, dtype, err, cap)
+    assert err <= cap
 
 
 # ---------------------------------------------------------------------------------------------------- sensitivity

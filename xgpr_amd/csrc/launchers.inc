@@ -15,6 +15,34 @@ template <typename K> int allow_big_lds(K kernel, size_t bytes) {
     return 0;
 }
 
+// One launch: the dynamic-LDS attribute where the kernel needs more than 64 KiB, the launch, the launch error under `what`.
+template <typename K, typename... Args>
+int launch(K kernel, dim3 grid, dim3 block, size_t lds, hipStream_t st, const char *what, Args... args) {
+    int rc = allow_big_lds(kernel, lds);
+    if (rc) return rc;
+    hipLaunchKernelGGL(kernel, grid, block, lds, st, args...);
+    HIP_TRY(hipGetLastError(), what);
+    return 0;
+}
+
+// A runtime flag as a template argument: f(std::true_type{}) or f(std::false_type{}).
+template <class F> int dispatch_bool(bool flag, F &&f) { return flag ? f(std::true_type{}) : f(std::false_type{}); }
+
+// The padded width as a template argument: f(std::integral_constant<int, LG>{}) for LO <= lg <= HI, `too_wide` otherwise.  The
+// bounds of a call site ARE the set of widths its kernel is instantiated for.
+template <int LO, int HI, class F> int dispatch_lg(int lg, const char *too_wide, F &&f) {
+    if constexpr (LO > HI) {
+        return fail(XGPR_ERR_UNSUPPORTED, too_wide);
+    } else {
+        if (lg == LO) return f(std::integral_constant<int, LO>{});
+        return dispatch_lg<LO + 1, HI>(lg, too_wide, f);
+    }
+}
+constexpr const char *TOO_WIDE_WAVE = "padded width > 1024 on this wave-tile kernel";
+constexpr const char *TOO_WIDE_Z3 = "padded width > 4096 on the wave path";      // the three-wave kernel (fused_ztz.inc) also serves 2048 and 4096 (round 6)
+constexpr const char *TOO_WIDE_WT = "padded width > 8192 on the wave-tile path"; // the wave-tile kernels in the input type (wave_tile.inc)
+constexpr int NO_ARM = 1;   // from a dispatch_lg callback: no instantiation for these arguments at this width, the caller goes on to its next plan
+
 int threads_for(long P) { return P >= 4096 ? 1024 : (P >= 512 ? 256 : 64); }
 
 template <typename T, bool SRHT>
@@ -28,17 +56,14 @@ int launch_fht(T *x, const int8_t *radem, long nvec, long P, hipStream_t st) {
         CH = cap;
     }
     const long nblocks = (total + CH - 1) / CH;
-    const size_t lds = (size_t)CH * sizeof(T);
-    auto kern = generic_fht_kernel<T, SRHT>;
-    int rc = allow_big_lds(kern, lds);
-    if (rc) return rc;
     const T nc = SRHT ? norm_constant<T>(P) : (T)1;
-    hipLaunchKernelGGL(kern, dim3((unsigned)nblocks), dim3(threads_for(CH)), lds, st, x, radem, total, (int)P, (int)CH, nc);
-    HIP_TRY(hipGetLastError(), "generic_fht_kernel launch");
+    int rc = launch(generic_fht_kernel<T, SRHT>, dim3((unsigned)nblocks), dim3(threads_for(CH)), (size_t)CH * sizeof(T), st,
+                    "generic_fht_kernel launch", x, radem, total, (int)P, (int)CH, nc);
+    if (rc) return rc;
     for (long h = CH; h < P; h <<= 1) {
         const long npairs = total / 2;
-        hipLaunchKernelGGL(global_stage_kernel<T>, dim3((unsigned)((npairs + 255) / 256)), dim3(256), 0, st, x, npairs, h);
-        HIP_TRY(hipGetLastError(), "global_stage_kernel launch");
+        rc = launch(global_stage_kernel<T>, dim3((unsigned)((npairs + 255) / 256)), dim3(256), 0, st, "global_stage_kernel launch", x, npairs, h);
+        if (rc) return rc;
     }
     return 0;
 }
@@ -59,74 +84,61 @@ int launch_generic_sorf(SorfArgs<T> a, void *workspace, size_t wbytes, hipStream
             return fail(XGPR_ERR_WORKSPACE, "workspace too small (see xgpr_sorf_workspace_bytes)");
         a.scratch = reinterpret_cast<T *>(workspace);
         const long nblocks = items < GENERIC_SCRATCH_SLOTS ? items : GENERIC_SCRATCH_SLOTS;
-        hipLaunchKernelGGL((generic_sorf_kernel<T, MODE, true>), dim3((unsigned)nblocks), dim3(1024), 0, st, a);
-        HIP_TRY(hipGetLastError(), "generic_sorf_kernel launch");
-        return 0;
+        return launch(generic_sorf_kernel<T, MODE, true>, dim3((unsigned)nblocks), dim3(1024), 0, st, "generic_sorf_kernel launch", a);
     }
-    const size_t lds = (size_t)a.P * sizeof(T);
-    auto kern = generic_sorf_kernel<T, MODE, false>;
-    int rc = allow_big_lds(kern, lds);
-    if (rc) return rc;
     const long nblocks = items < (1L << 20) ? items : (1L << 20);
-    hipLaunchKernelGGL(kern, dim3((unsigned)nblocks), dim3(threads_for(a.P)), lds, st, a);
-    HIP_TRY(hipGetLastError(), "generic_sorf_kernel launch");
-    return 0;
+    return launch(generic_sorf_kernel<T, MODE, false>, dim3((unsigned)nblocks), dim3(threads_for(a.P)), (size_t)a.P * sizeof(T), st,
+                  "generic_sorf_kernel launch", a);
 }
 
 int pack_masks(const int8_t *radem, uint64_t *masks, long R, int MW, hipStream_t st) {
     const long items = 3L * MW;
-    hipLaunchKernelGGL(pack_radem_kernel, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, st, radem, masks, R, MW);
-    HIP_TRY(hipGetLastError(), "pack_radem_kernel launch");
-    return 0;
+    return launch(pack_radem_kernel, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, st, "pack_radem_kernel launch", radem, masks, R, MW);
 }
 
 int masks_per_diag(long R) { return (int)(align_up((size_t)R, 1024) / 64); }
 size_t masks_bytes(long R) { return align_up((size_t)3 * masks_per_diag(R) * sizeof(uint64_t), 256); }
 
-#define DISPATCH_LOG2P(lg, CALL)                                                 \
-    switch (lg) {                                                                \
-        case 1: CALL(1); break; case 2: CALL(2); break; case 3: CALL(3); break;  \
-        case 4: CALL(4); break; case 5: CALL(5); break; case 6: CALL(6); break;  \
-        case 7: CALL(7); break; case 8: CALL(8); break; case 9: CALL(9); break;  \
-        case 10: CALL(10); break;                                                \
-        default: return fail(XGPR_ERR_UNSUPPORTED, "padded width > 1024 on this wave-tile kernel"); \
-    }
-
-// the three-wave kernel (fused_ztz.inc) also serves padded widths 2048 and 4096 (round 6)
-#define DISPATCH_LOG2P_Z3(lg, CALL)                                              \
-    switch (lg) {                                                                \
-        case 1: CALL(1); break; case 2: CALL(2); break; case 3: CALL(3); break;  \
-        case 4: CALL(4); break; case 5: CALL(5); break; case 6: CALL(6); break;  \
-        case 7: CALL(7); break; case 8: CALL(8); break; case 9: CALL(9); break;  \
-        case 10: CALL(10); break; case 11: CALL(11); break; case 12: CALL(12); break; \
-        default: return fail(XGPR_ERR_UNSUPPORTED, "padded width > 4096 on the wave path"); \
-    }
-
-// the wave-tile kernels in the input type (wave_tile.inc): padded widths up to 8192
-#define DISPATCH_LOG2P_WT(lg, CALL)                                              \
-    switch (lg) {                                                                \
-        case 1: CALL(1); break; case 2: CALL(2); break; case 3: CALL(3); break;  \
-        case 4: CALL(4); break; case 5: CALL(5); break; case 6: CALL(6); break;  \
-        case 7: CALL(7); break; case 8: CALL(8); break; case 9: CALL(9); break;  \
-        case 10: CALL(10); break; case 11: CALL(11); break; case 12: CALL(12); break; \
-        case 13: CALL(13); break;                                                \
-        default: return fail(XGPR_ERR_UNSUPPORTED, "padded width > 8192 on the wave-tile path"); \
-    }
-
+// `items` wave tiles, `waves` of them per workgroup (the independent-wave kernels: 4 waves; wave_tile.inc: WaveTile<T, LG>::WAVES)
 template <typename K, typename A> int launch_wave_tile(K kernel, const A &a, long items, int waves, size_t lds, hipStream_t st, const char *what) {
     const long nblocks = (items + waves - 1) / waves;
     if (nblocks > 2147483647L) return fail(XGPR_ERR_UNSUPPORTED, "too many datapoints for one launch");
-    int rc = allow_big_lds(kernel, lds);
-    if (rc) return rc;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)nblocks), dim3((unsigned)(waves * 64)), lds, st, a);
-    HIP_TRY(hipGetLastError(), what);
-    return 0;
+    return launch(kernel, dim3((unsigned)nblocks), dim3((unsigned)(waves * 64)), lds, st, what, a);
+}
+
+// the ordered sum of the partial-result slabs every slab-writing kernel ends with
+int reduce_slabs(const double *wpart, double *w_out, long num_rffs, long nslabs, hipStream_t st) {
+    return launch(reduce_slabs_kernel, dim3((unsigned)((num_rffs + 63) / 64)), dim3(256), 0, st, "reduce_slabs_kernel launch", wpart, w_out,
+                  num_rffs, nslabs);
 }
 
 void fill_norms(WaveArgs &a, int lg) {
     const float nc = norm_constant<float>(1L << lg);
     if (lg & 1) { a.nc = nc; a.chi_scale = 1.0f; }
     else { a.nc = 1.0f; a.chi_scale = nc * nc * nc; }   // exact power of two
+}
+
+// The fields every launch of the wave kernels shares (one wave = 1024 frequencies of a datapoint; `workspace` holds the packed sign
+// masks at its head: pack_masks stays the caller's own call).  The caller adds what is its own: outputs, grad, sigma, scale, seqlen,
+// the window fields of the sequence kernels.
+WaveArgs wave_args(const float *x, const float *chi, const void *workspace, long n, long row_stride, long d, long num_freqs, long R) {
+    WaveArgs a = {};
+    a.x = x; a.masks = (const uint64_t *)workspace; a.chi = chi;
+    a.n = n; a.row_stride = row_stride; a.F = num_freqs; a.d = (int)d;
+    a.MW = masks_per_diag(R); a.nb = (int)((num_freqs + 1023) / 1024);
+    fill_norms(a, ilog2(padded_width(d)));
+    return a;
+}
+
+// ... and of the kernels that read the Rademacher array itself (the any-width path, wave_tile.inc): P, reps, nc as well
+template <typename T>
+SorfArgs<T> sorf_args(const T *x, const int8_t *radem, const T *chi, long n, long row_stride, long d, long num_freqs, long R) {
+    const long P = padded_width(d);
+    SorfArgs<T> a = {};
+    a.x = x; a.radem = radem; a.chi = chi;
+    a.n = n; a.row_stride = row_stride; a.F = num_freqs; a.R = R; a.d = (int)d;
+    a.P = (int)P; a.reps = (int)((num_freqs + P - 1) / P); a.nc = norm_constant<T>(P);
+    return a;
 }
 
 // ------------------------------------------------------------------------------------
@@ -146,8 +158,25 @@ int check_seqlens(const int32_t *seqlen_host, long nseq, long n, long L, int con
     return 0;
 }
 
+// The shape checks every SORF entry point shares, in the reference's order (rbf_ops.cpp:49-62): the first failing one is reported.
+// `between`: the entry point's own checks that the reference makes after the frequency check and before the padded-width one (array
+// sizes of the gradient, sequence count, conv_width).  rffs_per_freq: 2 (cos, sin); 1 for max-pool.
+template <class Between>
+int check_sorf_shape(long n, long num_rffs, long num_freqs, long R, long P, int rffs_per_freq, Between &&between) {
+    if (n == 0) return fail(XGPR_ERR_NO_DATAPOINTS, "no datapoints");
+    if (num_rffs < 2 || (num_rffs & 1) != 0) return fail(XGPR_ERR_ODD_OUTPUT, "last dim of output must be even number");
+    if (rffs_per_freq * num_freqs != num_rffs || num_freqs > R) return fail(XGPR_ERR_RFFS_FREQS, "incorrect number of rffs and or freqs.");
+    if (int rc = between()) return rc;
+    if (R % P != 0) return fail(XGPR_ERR_RFFS_FREQS, "incorrect number of rffs and or freqs.");
+    return 0;
+}
+int check_sorf_shape(long n, long num_rffs, long num_freqs, long R, long P) {
+    return check_sorf_shape(n, num_rffs, num_freqs, R, P, 2, [] { return 0; });
+}
+
+// rbf_ops.cpp:64-69: the constant is rounded to T there; rbf_ops.cpp:180-185: a double constant in the gradient op (T = double: the
+// cast is the identity)
 template <typename T> double rbf_scale(long num_freqs, int fit_intercept) {
-    // rbf_ops.cpp:64-69: the constant is rounded to T there
     T s = fit_intercept ? (T)sqrt(1.0 / ((double)num_freqs - 0.5)) : (T)sqrt(1.0 / (double)num_freqs);
     return (double)s;
 }
@@ -179,6 +208,16 @@ int srht_impl(T *x, const int8_t *radem, long n, long dim, long radem_len, void 
 // at cfg3's shape and 0.436 against 0.46 at cfg2's -- taken; the float64 operator 1.72 against 1.62-1.68 (0.81 / 0.83 at
 // cfg2's shape): both plans sit at the same ~5.3-5.6 TB/s of write stream whatever the arithmetic in front of it, so the
 // operator keeps wave_rbf_kernel.  XGPR_FEAT_PLAN=wave / =z3 in the environment force one plan for both (A/B timing).
+// one launch of the three-wave kernel (fused_ztz.inc) in mode MODE at padded width 2^LG; a.dma1 picks the row fetch
+template <int LG, int MODE>
+int launch_ztz3(const WaveArgs &a, long ncols, int ngroups, size_t lds, hipStream_t st, const char *what) {
+    constexpr bool feat = MODE == Z3_FEAT64 || MODE == Z3_FEAT32;
+    return dispatch_bool(a.dma1 != 0, [&](auto DMA1) {
+        return launch(ztz3_kernel<LG, MODE, decltype(DMA1)::value>, dim3((unsigned)ncols, (unsigned)ngroups), dim3(z3_waves(LG, feat) * 64),
+                      lds, st, what, a);
+    });
+}
+
 template <int MODE>
 int launch_ztz3_feat(WaveArgs a, long P, int lg, hipStream_t st) {
     static const int forced = [] { const char *e = getenv("XGPR_FEAT_PLAN"); return !e ? 0 : e[0] == 'w' ? 1 : e[0] == 'z' ? 2 : 0; }();
@@ -197,17 +236,10 @@ int launch_ztz3_feat(WaveArgs a, long P, int lg, hipStream_t st) {
     const long by_rows = (a.n + a.G - 1) / a.G;
     if (ncols > by_rows) ncols = by_rows;
     const size_t lds3 = ztz3_lds_bytes(nbg, P, true);
-#define CALL_Z3F(LG)                                                                                          \
-    if constexpr (LG >= 5) {                                                                                  \
-        auto kern = a.dma1 ? ztz3_kernel<LG, MODE, true> : ztz3_kernel<LG, MODE, false>;                      \
-        int rc3 = allow_big_lds(kern, lds3);                                                                  \
-        if (rc3) return rc3;                                                                                  \
-        hipLaunchKernelGGL(kern, dim3((unsigned)ncols, (unsigned)ngroups), dim3(z3_waves(LG, true) * 64), lds3, st, a); \
-    }
-    DISPATCH_LOG2P_Z3(lg, CALL_Z3F)
-#undef CALL_Z3F
-    HIP_TRY(hipGetLastError(), "ztz3_kernel (feature rows) launch");
-    return 1;
+    const int rc = dispatch_lg<5, 12>(lg, TOO_WIDE_Z3, [&](auto LG) {
+        return launch_ztz3<decltype(LG)::value, MODE>(a, ncols, ngroups, lds3, st, "ztz3_kernel (feature rows) launch");
+    });
+    return rc ? rc : 1;
 }
 
 // XGPR_F64_PLAN=generic in the environment: the shapes of wave_tile.inc run on the any-width path instead (A/B timing)
@@ -221,72 +253,50 @@ int rbf_impl(const T *x, double *out, double *grad, const int8_t *radem, const T
              long out_rows, long num_rffs, long grad_rows, long grad_cols, long num_freqs, long R,
              double sigma, int fit_intercept, bool want_grad, void *workspace, size_t wbytes, void *stream) {
     const long P = padded_width(d);
-    if (n == 0 || out_rows != n) return fail(XGPR_ERR_NO_DATAPOINTS, "no datapoints");
-    if (num_rffs < 2 || (num_rffs & 1) != 0) return fail(XGPR_ERR_ODD_OUTPUT, "last dim of output must be even number");
-    if (2 * num_freqs != num_rffs || num_freqs > R) return fail(XGPR_ERR_RFFS_FREQS, "incorrect number of rffs and or freqs.");
-    if (want_grad && (grad_rows != out_rows || grad_cols != num_rffs)) return fail(XGPR_ERR_ARRAY_SIZES, "Wrong array sizes.");
-    if (R % P != 0) return fail(XGPR_ERR_RFFS_FREQS, "incorrect number of rffs and or freqs.");
+    if (out_rows != n) return fail(XGPR_ERR_NO_DATAPOINTS, "no datapoints");
+    int rc = check_sorf_shape(n, num_rffs, num_freqs, R, P, 2, [&] {
+        return want_grad && (grad_rows != out_rows || grad_cols != num_rffs) ? fail(XGPR_ERR_ARRAY_SIZES, "Wrong array sizes.") : 0;
+    });
+    if (rc) return rc;
     if (!aligned16(out)) return fail(XGPR_ERR_WORKSPACE, "output pointer must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
-    const int reps = (int)((num_freqs + P - 1) / P);
+    const int lg = ilog2(P);
 
     if constexpr (sizeof(T) == 4) {
-        if (P <= 1024) {
-            if (!workspace || wbytes < masks_bytes(R)) return fail(XGPR_ERR_WORKSPACE, "workspace too small (see xgpr_rbf_workspace_bytes)");
-            WaveArgs a = {};
-            a.x = x; a.out = out; a.masks = (const uint64_t *)workspace; a.chi = chi;
-            a.n = n; a.row_stride = d; a.F = num_freqs; a.d = (int)d;
-            a.MW = masks_per_diag(R); a.nb = (int)((num_freqs + 1023) / 1024);
+        // one wave per tile of 1024 frequencies: wave_rbf_kernel up to P = 1024 (there a missing workspace is an error); at 2048 / 4096
+        // the feature operator on the three-wave kernel's wide transforms (fused_ztz.inc, Z3_FEAT64), taken only with a workspace that
+        // holds the masks -- without one, and for the gradient, the plans further down serve these widths
+        const bool have_masks = workspace && wbytes >= masks_bytes(R);
+        if (P <= 1024 && !have_masks) return fail(XGPR_ERR_WORKSPACE, "workspace too small (see xgpr_rbf_workspace_bytes)");
+        if (P <= 1024 || (P <= 4096 && !want_grad && have_masks)) {
+            WaveArgs a = wave_args(x, chi, workspace, n, d, d, num_freqs, R);
+            a.out = out;
             a.scale = rbf_scale<float>(num_freqs, fit_intercept);
             if (want_grad) {
                 if (!aligned16(grad)) return fail(XGPR_ERR_WORKSPACE, "gradient pointer must be 16-byte aligned");
                 a.grad = grad; a.sigma = sigma;
-                a.scale = fit_intercept ? sqrt(1.0 / ((double)num_freqs - 0.5)) : sqrt(1.0 / (double)num_freqs);
+                a.scale = rbf_scale<double>(num_freqs, fit_intercept);
             }
-            const int lg = ilog2(P);
-            fill_norms(a, lg);
-            int rc = pack_masks(radem, (uint64_t *)workspace, R, a.MW, st);
+            rc = pack_masks(radem, (uint64_t *)workspace, R, a.MW, st);
             if (rc) return rc;
-            const long items = n * a.nb;
-            const long nblocks = (items + 3) / 4;
-            if (nblocks > 2147483647L) return fail(XGPR_ERR_UNSUPPORTED, "too many datapoints for one launch");
+            const long nblocks = (n * a.nb + 3) / 4;
+            if (P <= 1024 && nblocks > 2147483647L) return fail(XGPR_ERR_UNSUPPORTED, "too many datapoints for one launch");
             if (!want_grad) {
                 const int rcf = launch_ztz3_feat<Z3_FEAT64>(a, P, lg, st);
                 if (rcf != 0) return rcf < 0 ? rcf : 0;
             }
-            if (want_grad) {
-#define CALL_RBFG(LG) hipLaunchKernelGGL((wave_rbf_kernel<LG, OUT_GRAD>), dim3((unsigned)nblocks), dim3(256), 0, st, a)
-                DISPATCH_LOG2P(lg, CALL_RBFG)
-#undef CALL_RBFG
-            } else {
-#define CALL_RBF(LG) hipLaunchKernelGGL((wave_rbf_kernel<LG, OUT_F64>), dim3((unsigned)nblocks), dim3(256), 0, st, a)
-                DISPATCH_LOG2P(lg, CALL_RBF)
-#undef CALL_RBF
-            }
-            HIP_TRY(hipGetLastError(), "wave_rbf_kernel launch");
-            return 0;
+            if (P <= 1024)
+                return dispatch_lg<1, 10>(lg, TOO_WIDE_WAVE, [&](auto LG) {
+                    return dispatch_bool(want_grad, [&](auto GRAD) {
+                        return launch(wave_rbf_kernel<decltype(LG)::value, decltype(GRAD)::value ? OUT_GRAD : OUT_F64>, dim3((unsigned)nblocks),
+                                      dim3(256), 0, st, "wave_rbf_kernel launch", a);
+                    });
+                });
         }
     }
-    if constexpr (sizeof(T) == 4) {
-        // padded widths 2048 / 4096: the feature operator on the three-wave kernel's wide transforms (fused_ztz.inc, Z3_FEAT64)
-        if (P <= 4096 && !want_grad && workspace && wbytes >= masks_bytes(R)) {
-            WaveArgs a = {};
-            a.x = x; a.out = out; a.masks = (const uint64_t *)workspace; a.chi = chi;
-            a.n = n; a.row_stride = d; a.F = num_freqs; a.d = (int)d;
-            a.MW = masks_per_diag(R); a.nb = (int)((num_freqs + 1023) / 1024);
-            a.scale = rbf_scale<float>(num_freqs, fit_intercept);
-            const int lg = ilog2(P);
-            fill_norms(a, lg);
-            int rc = pack_masks(radem, (uint64_t *)workspace, R, a.MW, st);
-            if (rc) return rc;
-            const int rcf = launch_ztz3_feat<Z3_FEAT64>(a, P, lg, st);
-            if (rcf != 0) return rcf < 0 ? rcf : 0;
-        }
-    }
-    SorfArgs<T> a = {};
-    a.x = x; a.out = out; a.grad = grad; a.radem = radem; a.chi = chi;
-    a.n = n; a.row_stride = d; a.F = num_freqs; a.R = R; a.d = (int)d;
-    a.P = (int)P; a.reps = reps; a.nc = norm_constant<T>(P); a.sigma = sigma;
+    SorfArgs<T> a = sorf_args(x, radem, chi, n, d, d, num_freqs, R);
+    a.out = out; a.grad = grad; a.sigma = sigma;
+    a.scale = want_grad ? rbf_scale<double>(num_freqs, fit_intercept) : rbf_scale<T>(num_freqs, fit_intercept);
     {
         // wave tiles in registers + an LDS image (wave_tile.inc): the float64 feature and gradient operators at P <= 8192, the float32
         // gradient operator at 2048 <= P <= 8192 and the float32 feature operator at P = 8192 (narrower ones are served above);
@@ -298,24 +308,22 @@ int rbf_impl(const T *x, double *out, double *grad, const int8_t *radem, const T
             // 8-byte aligned gets two 8-byte stores per pair from the same kernel -- the any-width path evaluates cos / sin with the
             // library's routine, so sending the view there would make the last bit of the result depend on the pointer
             a.grad_split = want_grad && !aligned16(grad);
-            // rbf_ops.cpp:180-185: a double constant in the gradient op
-            a.scale = want_grad ? (fit_intercept ? sqrt(1.0 / ((double)num_freqs - 0.5)) : sqrt(1.0 / (double)num_freqs)) : (double)rbf_scale<T>(num_freqs, fit_intercept);
             const long items = n * (P > 1024 ? R / 1024 : (num_freqs + 1023) / 1024);
-#define CALL_RBFT(LG) if constexpr (sizeof(T) == 8 || LG > 10) { \
-                using WT = WaveTile<T, LG>; \
-                if (want_grad) return launch_wave_tile(wave_tile_rbf_kernel<T, LG, true>, a, items, WT::WAVES, WT::LDS_BYTES, st, "wave_tile_rbf_kernel launch"); \
-                if constexpr (sizeof(T) == 8 || LG > 12) \
-                    return launch_wave_tile(wave_tile_rbf_kernel<T, LG, false>, a, items, WT::WAVES, WT::LDS_BYTES, st, "wave_tile_rbf_kernel launch"); }
-            DISPATCH_LOG2P_WT(ilog2(P), CALL_RBFT)
-#undef CALL_RBFT
+            rc = dispatch_lg<1, 13>(lg, TOO_WIDE_WT, [&](auto LGc) {
+                constexpr int LG = decltype(LGc)::value;
+                if constexpr (sizeof(T) == 8 || LG > 10) {
+                    using WT = WaveTile<T, LG>;
+                    if (want_grad)
+                        return launch_wave_tile(wave_tile_rbf_kernel<T, LG, true>, a, items, WT::WAVES, WT::LDS_BYTES, st, "wave_tile_rbf_kernel launch");
+                    if constexpr (sizeof(T) == 8 || LG > 12)
+                        return launch_wave_tile(wave_tile_rbf_kernel<T, LG, false>, a, items, WT::WAVES, WT::LDS_BYTES, st, "wave_tile_rbf_kernel launch");
+                }
+                return NO_ARM;
+            });
+            if (rc != NO_ARM) return rc;
         }
     }
-    if (want_grad) {
-        // rbf_ops.cpp:180-185: a double constant in the gradient op
-        a.scale = fit_intercept ? sqrt(1.0 / ((double)num_freqs - 0.5)) : sqrt(1.0 / (double)num_freqs);
-        return launch_generic_sorf<T, MODE_RBF_GRAD>(a, workspace, wbytes, st);
-    }
-    a.scale = rbf_scale<T>(num_freqs, fit_intercept);
+    if (want_grad) return launch_generic_sorf<T, MODE_RBF_GRAD>(a, workspace, wbytes, st);
     return launch_generic_sorf<T, MODE_RBF>(a, workspace, wbytes, st);
 }
 
@@ -330,14 +338,19 @@ size_t conv_rows_stage_offset(long R, long P, long nseq) {
 }
 constexpr size_t CONV_ROWS_STAGE_BYTES = (size_t)256 << 20;      // float64 staging of the any-width windows: at most this much is asked for
 
-size_t conv_rows_workspace_bytes(long R, long width, long num_rffs, long nseq) {
+// (2048 / 4096 too: the staged route serves them when radem is not 16-byte aligned.)  narrays: 1 for the feature rows; 2 for the feature
+// AND gradient rows (xgpr_conv_grad_rows_f32, mode MODE_CONV_GRAD_ROWS of conv_impl: outf = zrows[n, num_rffs], gradf = grows[n, num_rffs]
+// -- the dispatch of the feature rows with the gradient operator's kernels: windows up to 1024 elements wave_conv_kernel<LG,
+// CONV_GRAD_ROWS>, 2048 / 4096 wave_tile_conv_kernel<float, LG, MODE_CONV_GRAD_ROWS>, every other shape the float64 gradient operator
+// slice by slice into TWO float64 staging arrays (out, grad) -- together within CONV_ROWS_STAGE_BYTES -- and one rounding pass each).
+size_t conv_rows_workspace_bytes(long R, long width, long num_rffs, long nseq, int narrays) {
     const long P = padded_width(width);
     size_t b = conv_rows_stage_offset(R, P, nseq);
-    if (P > 1024 && nseq > 0 && num_rffs > 0) {      // (2048 / 4096 too: the staged route serves them when radem is not 16-byte aligned)
-        const size_t row = (size_t)num_rffs * sizeof(double);
-        size_t rows = CONV_ROWS_STAGE_BYTES / row > 0 ? CONV_ROWS_STAGE_BYTES / row : 1;
+    if (P > 1024 && nseq > 0 && num_rffs > 0) {
+        const size_t row = (size_t)num_rffs * sizeof(double), per_array = CONV_ROWS_STAGE_BYTES / narrays;
+        size_t rows = per_array / row > 0 ? per_array / row : 1;
         if (rows > (size_t)nseq) rows = (size_t)nseq;
-        b += align_up(rows * row, 256);
+        b += narrays * align_up(rows * row, 256);
     }
     return b;
 }
@@ -351,30 +364,21 @@ __global__ __launch_bounds__(256) void round_rows_kernel(const double2 *__restri
     dst[idx] = make_float2(c, (float)v.y);
 }
 
-int conv_rows_staged(const float *x, float *zc, const int8_t *radem, const float *chi, const int32_t *seqlen_host,
-                     const int32_t *seqlen_dev, long n, long L, long C, long num_rffs, long num_freqs, long R, int conv_width,
-                     int scaling_type, int fit_intercept, void *workspace, size_t wbytes, hipStream_t st);
+// the staged route of both row modes: zrows, and grows as well when it is not NULL
+int conv_rows_staged(const float *x, float *zrows, float *grows, const int8_t *radem, const float *chi, const int32_t *seqlen_host,
+                     const int32_t *seqlen_dev, long n, long L, long C, long num_rffs, long num_freqs, long R, double sigma,
+                     int conv_width, int scaling_type, int fit_intercept, void *workspace, size_t wbytes, hipStream_t st);
 
-// ---- float32 feature AND gradient rows of the sequence kernels (xgpr_conv_grad_rows_f32, mode MODE_CONV_GRAD_ROWS of conv_impl): outf =
-// zrows[n, num_rffs], gradf = grows[n, num_rffs].  The dispatch of the feature rows above with the gradient operator's kernels: windows up
-// to 1024 elements wave_conv_kernel<LG, CONV_GRAD_ROWS>, 2048 / 4096 wave_tile_conv_kernel<float, LG, MODE_CONV_GRAD_ROWS>, every other
-// shape the float64 gradient operator slice by slice into TWO float64 staging arrays (out, grad) behind the operator's own workspace --
-// together within CONV_ROWS_STAGE_BYTES -- and one rounding pass each.
-size_t conv_grad_rows_workspace_bytes(long R, long width, long num_rffs, long nseq) {
-    const long P = padded_width(width);
-    size_t b = conv_rows_stage_offset(R, P, nseq);
-    if (P > 1024 && nseq > 0 && num_rffs > 0) {
-        const size_t row = (size_t)num_rffs * sizeof(double), half = CONV_ROWS_STAGE_BYTES / 2;
-        size_t rows = half / row > 0 ? half / row : 1;
-        if (rows > (size_t)nseq) rows = (size_t)nseq;
-        b += 2 * align_up(rows * row, 256);
+// the sequence kernels' mode as wave_conv_kernel's template argument: f(std::integral_constant<int, CONV_*>{})
+template <class F> int dispatch_conv_mode(int mode, F &&f) {
+    switch (mode) {
+        case MODE_CONV_GRAD: return f(std::integral_constant<int, CONV_GRAD>{});
+        case MODE_CONV_GRAD_ROWS: return f(std::integral_constant<int, CONV_GRAD_ROWS>{});
+        case MODE_CONV_ROWS: return f(std::integral_constant<int, CONV_ROWS>{});
+        case MODE_MAXPOOL: return f(std::integral_constant<int, CONV_MAXPOOL>{});
+        default: return f(std::integral_constant<int, CONV_FGEN>{});
     }
-    return b;
 }
-
-int conv_grad_rows_staged(const float *x, float *zrows, float *grows, const int8_t *radem, const float *chi, const int32_t *seqlen_host,
-                          const int32_t *seqlen_dev, long n, long L, long C, long num_rffs, long num_freqs, long R, double sigma,
-                          int conv_width, int scaling_type, int fit_intercept, void *workspace, size_t wbytes, hipStream_t st);
 
 template <typename T>
 int conv_impl(const T *x, double *out, double *grad, float *outf, const int8_t *radem, const T *chi,
@@ -385,23 +389,20 @@ int conv_impl(const T *x, double *out, double *grad, float *outf, const int8_t *
     const bool rows_mode = mode == MODE_CONV_ROWS || mode == MODE_CONV_GRAD_ROWS;      // float32 rows out: no float64 output to check
     const bool grad_mode = mode == MODE_CONV_GRAD || mode == MODE_CONV_GRAD_ROWS;
     if (rows_mode && sizeof(T) != 4) return fail(XGPR_ERR_UNSUPPORTED, "float32 feature rows take float32 input");
-    if (n == 0 || out_rows != n) return fail(XGPR_ERR_NO_DATAPOINTS, "no datapoints");
-    if (num_rffs < 2 || (num_rffs & 1) != 0) return fail(XGPR_ERR_ODD_OUTPUT, "last dim of output must be even number");
-    if (mode == MODE_MAXPOOL) {
-        if (num_freqs != num_rffs || num_freqs > R) return fail(XGPR_ERR_RFFS_FREQS, "incorrect number of rffs and or freqs.");
-    } else {
-        if (2 * num_freqs != num_rffs || num_freqs > R) return fail(XGPR_ERR_RFFS_FREQS, "incorrect number of rffs and or freqs.");
-    }
-    if (mode == MODE_CONV_GRAD && (grad_rows != out_rows || grad_cols != num_rffs))
-        return fail(XGPR_ERR_ARRAY_SIZES, "Wrong array sizes.");
-    if (nseq != n) return fail(XGPR_ERR_SEQLEN_SIZE, "wrong array sizes");
-    if (L < conv_width || conv_width <= 0) return fail(XGPR_ERR_CONV_WIDTH, "invalid conv_width");
+    if (out_rows != n) return fail(XGPR_ERR_NO_DATAPOINTS, "no datapoints");
     const long win = (long)conv_width * C;
     const long P = padded_width(win);
     const int reps = (int)((num_freqs + P - 1) / P);
-    if (R % P != 0) return fail(XGPR_ERR_RFFS_FREQS, "incorrect number of rffs and or freqs.");
+    int rc = check_sorf_shape(n, num_rffs, num_freqs, R, P, mode == MODE_MAXPOOL ? 1 : 2, [&] {
+        if (mode == MODE_CONV_GRAD && (grad_rows != out_rows || grad_cols != num_rffs))
+            return fail(XGPR_ERR_ARRAY_SIZES, "Wrong array sizes.");
+        if (nseq != n) return fail(XGPR_ERR_SEQLEN_SIZE, "wrong array sizes");
+        if (L < conv_width || conv_width <= 0) return fail(XGPR_ERR_CONV_WIDTH, "invalid conv_width");
+        return 0;
+    });
+    if (rc) return rc;
     if (mode == MODE_MAXPOOL && R != (long)reps * P) return fail(XGPR_ERR_RFFS_FREQS, "incorrect number of rffs and or freqs.");
-    int rc = check_seqlens(seqlen_host, nseq, n, L, conv_width);
+    rc = check_seqlens(seqlen_host, nseq, n, L, conv_width);
     if (rc) return rc;
     if (!seqlen_dev) return fail(XGPR_ERR_WORKSPACE, "seqlen_dev (device copy of the sequence lengths) is required");
     hipStream_t st = (hipStream_t)stream;
@@ -409,21 +410,18 @@ int conv_impl(const T *x, double *out, double *grad, float *outf, const int8_t *
         return fail(XGPR_ERR_WORKSPACE, "feature rows pointer must be 8-byte aligned");
     if (mode == MODE_CONV_GRAD_ROWS && (!gradf || (reinterpret_cast<uintptr_t>(gradf) & 7) != 0))
         return fail(XGPR_ERR_WORKSPACE, "gradient rows pointer must be 8-byte aligned");
+    const int lg = ilog2(P);
 
     if constexpr (sizeof(T) == 4) {
         if (P <= 1024) {
             if (mode != MODE_MAXPOOL && !rows_mode && !aligned16(out)) return fail(XGPR_ERR_WORKSPACE, "output pointer must be 16-byte aligned");
             if (mode == MODE_CONV_GRAD && !aligned16(grad)) return fail(XGPR_ERR_WORKSPACE, "gradient pointer must be 16-byte aligned");
             if (!workspace || wbytes < masks_bytes(R)) return fail(XGPR_ERR_WORKSPACE, "workspace too small (see xgpr_rbf_workspace_bytes)");
-            WaveArgs a = {};
-            a.x = x; a.out = out; a.outf = outf; a.masks = (const uint64_t *)workspace; a.chi = chi; a.seqlen = seqlen_dev;
-            a.n = n; a.row_stride = L * C; a.F = num_freqs; a.d = (int)win; a.kmer_stride = (int)C;
+            WaveArgs a = wave_args(x, chi, workspace, n, L * C, win, num_freqs, R);
+            a.out = out; a.outf = outf; a.seqlen = seqlen_dev; a.kmer_stride = (int)C;
             a.conv_width = conv_width; a.scaling_type = scaling_type; a.fit_intercept = fit_intercept;
-            a.MW = masks_per_diag(R); a.nb = (int)((num_freqs + 1023) / 1024);
             a.scale = sqrt(1.0 / (double)num_freqs);
             if (grad_mode) { a.grad = grad; a.gradf = gradf; a.sigma = sigma; }
-            const int lg = ilog2(P);
-            fill_norms(a, lg);
             rc = pack_masks(radem, (uint64_t *)workspace, R, a.MW, st);
             if (rc) return rc;
             const long nblocks = (n * a.nb + 3) / 4;
@@ -433,42 +431,23 @@ int conv_impl(const T *x, double *out, double *grad, float *outf, const int8_t *
             const size_t order_off = masks_bytes(R);
             if (n >= 64 && n <= 2147483647L && L <= 12000 && wbytes >= order_off + (size_t)n * sizeof(int32_t)) {
                 int32_t *order = reinterpret_cast<int32_t *>(reinterpret_cast<unsigned char *>(workspace) + order_off);
-                hipLaunchKernelGGL(conv_order_kernel, dim3(1), dim3(1024), (size_t)(L + 1) * sizeof(int), st, seqlen_dev, order, n, (int)L);
-                HIP_TRY(hipGetLastError(), "conv_order_kernel launch");
+                rc = launch(conv_order_kernel, dim3(1), dim3(1024), (size_t)(L + 1) * sizeof(int), st, "conv_order_kernel launch", seqlen_dev,
+                            order, n, (int)L);
+                if (rc) return rc;
                 a.order = order;
             }
-#define CALL_CONV(LG, CM) hipLaunchKernelGGL((wave_conv_kernel<LG, CM>), dim3((unsigned)nblocks), dim3(256), 0, st, a)
-            if (mode == MODE_CONV_GRAD) {
-#define CALL_CONV_G(LG) CALL_CONV(LG, CONV_GRAD)
-                DISPATCH_LOG2P(lg, CALL_CONV_G)
-#undef CALL_CONV_G
-            } else if (mode == MODE_CONV_GRAD_ROWS) {
-#define CALL_CONV_GR(LG) CALL_CONV(LG, CONV_GRAD_ROWS)
-                DISPATCH_LOG2P(lg, CALL_CONV_GR)
-#undef CALL_CONV_GR
-            } else if (mode == MODE_CONV_ROWS) {
-#define CALL_CONV_R(LG) CALL_CONV(LG, CONV_ROWS)
-                DISPATCH_LOG2P(lg, CALL_CONV_R)
-#undef CALL_CONV_R
-            } else if (mode != MODE_MAXPOOL) {
-#define CALL_CONV_F(LG) CALL_CONV(LG, CONV_FGEN)
-                DISPATCH_LOG2P(lg, CALL_CONV_F)
-#undef CALL_CONV_F
-            } else {
-#define CALL_CONV_M(LG) CALL_CONV(LG, CONV_MAXPOOL)
-                DISPATCH_LOG2P(lg, CALL_CONV_M)
-#undef CALL_CONV_M
-            }
-#undef CALL_CONV
-            HIP_TRY(hipGetLastError(), "wave_conv_kernel launch");
-            return 0;
+            return dispatch_lg<1, 10>(lg, TOO_WIDE_WAVE, [&](auto LG) {
+                return dispatch_conv_mode(mode, [&](auto CM) {
+                    return launch(wave_conv_kernel<decltype(LG)::value, decltype(CM)::value>, dim3((unsigned)nblocks), dim3(256), 0, st,
+                                  "wave_conv_kernel launch", a);
+                });
+            });
         }
     }
-    SorfArgs<T> a = {};
-    a.x = x; a.out = out; a.grad = grad; a.outf = outf; a.gradf = gradf; a.radem = radem; a.chi = chi; a.seqlen = seqlen_dev;
-    a.n = n; a.row_stride = L * C; a.F = num_freqs; a.R = R; a.d = (int)win; a.kmer_stride = (int)C;
-    a.conv_width = conv_width; a.P = (int)P; a.reps = reps; a.scaling_type = scaling_type;
-    a.nc = norm_constant<T>(P); a.scale = sqrt(1.0 / (double)num_freqs); a.sigma = sigma; a.fit_intercept = fit_intercept;
+    SorfArgs<T> a = sorf_args(x, radem, chi, n, L * C, win, num_freqs, R);
+    a.out = out; a.grad = grad; a.outf = outf; a.gradf = gradf; a.seqlen = seqlen_dev; a.kmer_stride = (int)C;
+    a.conv_width = conv_width; a.scaling_type = scaling_type;
+    a.scale = sqrt(1.0 / (double)num_freqs); a.sigma = sigma; a.fit_intercept = fit_intercept;
     {
         // wave tiles in registers + an LDS image (wave_tile.inc): float64 input at every padded window width up to 4096, float32 input at
         // 2048 / 4096 (narrower float32 windows were served above); XGPR_F64_PLAN=generic keeps the any-width path (A/B)
@@ -477,27 +456,31 @@ int conv_impl(const T *x, double *out, double *grad, float *outf, const int8_t *
         const bool aligned = mode == MODE_MAXPOOL || rows_mode || (aligned16(out) && (mode != MODE_CONV_GRAD || aligned16(grad)));
         if (mine && !generic64 && aligned && R % 64 == 0 && (reinterpret_cast<uintptr_t>(radem) & 15) == 0) {
             const long items = n * (P > 1024 ? R / 1024 : (num_freqs + 1023) / 1024);
-#define CALL_CONVT(LG) if constexpr ((sizeof(T) == 8 || LG > 10) && LG <= 12) { \
-                using WT = WaveTile<T, LG>; \
-                if (mode == MODE_CONV) return launch_wave_tile(wave_tile_conv_kernel<T, LG, MODE_CONV>, a, items, WT::WAVES, WT::LDS_BYTES, st, "wave_tile_conv_kernel launch"); \
-                if constexpr (sizeof(T) == 4) { if (mode == MODE_CONV_ROWS) return launch_wave_tile(wave_tile_conv_kernel<T, LG, MODE_CONV_ROWS>, a, items, WT::WAVES, WT::LDS_BYTES, st, "wave_tile_conv_kernel launch"); } \
-                if constexpr (sizeof(T) == 4) { if (mode == MODE_CONV_GRAD_ROWS) return launch_wave_tile(wave_tile_conv_kernel<T, LG, MODE_CONV_GRAD_ROWS>, a, items, WT::WAVES, WT::LDS_BYTES, st, "wave_tile_conv_kernel launch"); } \
-                if (mode == MODE_CONV_GRAD) return launch_wave_tile(wave_tile_conv_kernel<T, LG, MODE_CONV_GRAD>, a, items, WT::WAVES, WT::LDS_BYTES, st, "wave_tile_conv_kernel launch"); \
-                return launch_wave_tile(wave_tile_conv_kernel<T, LG, MODE_MAXPOOL>, a, items, WT::WAVES, WT::LDS_BYTES, st, "wave_tile_conv_kernel launch"); }
-            DISPATCH_LOG2P_WT(ilog2(P), CALL_CONVT)
-#undef CALL_CONVT
+            rc = dispatch_lg<1, 13>(lg, TOO_WIDE_WT, [&](auto LGc) {
+                constexpr int LG = decltype(LGc)::value;
+                if constexpr ((sizeof(T) == 8 || LG > 10) && LG <= 12) {
+                    using WT = WaveTile<T, LG>;
+                    const char *what = "wave_tile_conv_kernel launch";
+                    if (mode == MODE_CONV) return launch_wave_tile(wave_tile_conv_kernel<T, LG, MODE_CONV>, a, items, WT::WAVES, WT::LDS_BYTES, st, what);
+                    if constexpr (sizeof(T) == 4) {      // the float32 row modes
+                        if (mode == MODE_CONV_ROWS)
+                            return launch_wave_tile(wave_tile_conv_kernel<T, LG, MODE_CONV_ROWS>, a, items, WT::WAVES, WT::LDS_BYTES, st, what);
+                        if (mode == MODE_CONV_GRAD_ROWS)
+                            return launch_wave_tile(wave_tile_conv_kernel<T, LG, MODE_CONV_GRAD_ROWS>, a, items, WT::WAVES, WT::LDS_BYTES, st, what);
+                    }
+                    if (mode == MODE_CONV_GRAD)
+                        return launch_wave_tile(wave_tile_conv_kernel<T, LG, MODE_CONV_GRAD>, a, items, WT::WAVES, WT::LDS_BYTES, st, what);
+                    return launch_wave_tile(wave_tile_conv_kernel<T, LG, MODE_MAXPOOL>, a, items, WT::WAVES, WT::LDS_BYTES, st, what);
+                }
+                return NO_ARM;
+            });
+            if (rc != NO_ARM) return rc;
         }
     }
-    if (mode == MODE_CONV_ROWS) {
+    if (rows_mode) {
         if constexpr (sizeof(T) == 4)
-            return conv_rows_staged(x, outf, radem, chi, seqlen_host, seqlen_dev, n, L, C, num_rffs, num_freqs, R, conv_width, scaling_type,
-                                    fit_intercept, workspace, wbytes, st);
-        else return fail(XGPR_ERR_UNSUPPORTED, "float32 feature rows take float32 input");
-    }
-    if (mode == MODE_CONV_GRAD_ROWS) {
-        if constexpr (sizeof(T) == 4)
-            return conv_grad_rows_staged(x, outf, gradf, radem, chi, seqlen_host, seqlen_dev, n, L, C, num_rffs, num_freqs, R, sigma, conv_width,
-                                         scaling_type, fit_intercept, workspace, wbytes, st);
+            return conv_rows_staged(x, outf, mode == MODE_CONV_GRAD_ROWS ? gradf : nullptr, radem, chi, seqlen_host, seqlen_dev, n, L, C,
+                                    num_rffs, num_freqs, R, sigma, conv_width, scaling_type, fit_intercept, workspace, wbytes, st);
         else return fail(XGPR_ERR_UNSUPPORTED, "float32 feature rows take float32 input");
     }
     if (mode == MODE_CONV) return launch_generic_sorf<T, MODE_CONV>(a, workspace, wbytes, st);
@@ -505,65 +488,45 @@ int conv_impl(const T *x, double *out, double *grad, float *outf, const int8_t *
     return launch_generic_sorf<T, MODE_MAXPOOL>(a, workspace, wbytes, st);
 }
 
-int conv_rows_staged(const float *x, float *zc, const int8_t *radem, const float *chi, const int32_t *seqlen_host,
-                     const int32_t *seqlen_dev, long n, long L, long C, long num_rffs, long num_freqs, long R, int conv_width,
-                     int scaling_type, int fit_intercept, void *workspace, size_t wbytes, hipStream_t st) {
+int conv_rows_staged(const float *x, float *zrows, float *grows, const int8_t *radem, const float *chi, const int32_t *seqlen_host,
+                     const int32_t *seqlen_dev, long n, long L, long C, long num_rffs, long num_freqs, long R, double sigma,
+                     int conv_width, int scaling_type, int fit_intercept, void *workspace, size_t wbytes, hipStream_t st) {
     const long P = padded_width((long)conv_width * C);
     const size_t off = conv_rows_stage_offset(R, P, n), row = (size_t)num_rffs * sizeof(double);
-    if (!workspace || !aligned16(workspace) || wbytes < off + row)
-        return fail(XGPR_ERR_WORKSPACE, "workspace too small (see xgpr_conv_feature_rows_workspace_bytes)");
-    double *stage = reinterpret_cast<double *>(reinterpret_cast<unsigned char *>(workspace) + off);
-    long rows = (long)((wbytes - off) / row);
-    if (rows > n) rows = n;
-    for (long lo = 0; lo < n; lo += rows) {
-        const long cnt = n - lo < rows ? n - lo : rows;
-        HIP_TRY(hipMemsetAsync(stage, 0, (size_t)cnt * row, st), "hipMemsetAsync (feature rows staging)");
-        int rc = conv_impl<float>(x + lo * L * C, stage, nullptr, nullptr, radem, chi, seqlen_host + lo, seqlen_dev + lo, cnt, L, C, cnt,
-                                  num_rffs, 0, 0, num_freqs, R, cnt, 0.0, conv_width, scaling_type, MODE_CONV, workspace, off, (void *)st);
-        if (rc) return rc;
-        const long npairs = cnt * (num_rffs / 2);
-        const long nblocks = (npairs + 255) / 256;
-        if (nblocks > 2147483647L) return fail(XGPR_ERR_UNSUPPORTED, "staging slice too large for one rounding launch");
-        hipLaunchKernelGGL(round_rows_kernel, dim3((unsigned)nblocks), dim3(256), 0, st, reinterpret_cast<const double2 *>(stage),
-                           reinterpret_cast<float2 *>(zc + lo * num_rffs), npairs, num_rffs / 2, fit_intercept);
-        HIP_TRY(hipGetLastError(), "round_rows_kernel launch");
-    }
-    return 0;
-}
-
-int conv_grad_rows_staged(const float *x, float *zrows, float *grows, const int8_t *radem, const float *chi, const int32_t *seqlen_host,
-                          const int32_t *seqlen_dev, long n, long L, long C, long num_rffs, long num_freqs, long R, double sigma,
-                          int conv_width, int scaling_type, int fit_intercept, void *workspace, size_t wbytes, hipStream_t st) {
-    const long P = padded_width((long)conv_width * C);
-    const size_t off = conv_rows_stage_offset(R, P, n), row = (size_t)num_rffs * sizeof(double);
-    // two arrays of `half` bytes each (a multiple of 256: both 16-byte aligned, as the float64 operator's double2 accesses need)
-    const size_t half = (!workspace || wbytes < off) ? 0 : (wbytes - off) / 2 / 256 * 256;
-    if (!workspace || !aligned16(workspace) || half < row)
-        return fail(XGPR_ERR_WORKSPACE, "workspace too small (see xgpr_conv_grad_rows_workspace_bytes)");
+    const size_t room = (!workspace || wbytes < off) ? 0 : wbytes - off;
+    // one array: all the room; two arrays: half each, a multiple of 256 bytes (both 16-byte aligned, as the float64 operator's double2
+    // accesses need)
+    const size_t per_array = grows ? room / 2 / 256 * 256 : room;
+    if (!workspace || !aligned16(workspace) || per_array < row)
+        return fail(XGPR_ERR_WORKSPACE, grows ? "workspace too small (see xgpr_conv_grad_rows_workspace_bytes)"
+                                              : "workspace too small (see xgpr_conv_feature_rows_workspace_bytes)");
+    const char *memset_what = grows ? "hipMemsetAsync (gradient rows staging)" : "hipMemsetAsync (feature rows staging)";
     double *stage_z = reinterpret_cast<double *>(reinterpret_cast<unsigned char *>(workspace) + off);
-    double *stage_g = reinterpret_cast<double *>(reinterpret_cast<unsigned char *>(workspace) + off + half);
-    long rows = (long)(half / row);
+    double *stage_g = grows ? reinterpret_cast<double *>(reinterpret_cast<unsigned char *>(workspace) + off + per_array) : nullptr;
+    long rows = (long)(per_array / row);
     if (rows > n) rows = n;
     for (long lo = 0; lo < n; lo += rows) {
         const long cnt = n - lo < rows ? n - lo : rows;
-        HIP_TRY(hipMemsetAsync(stage_z, 0, (size_t)cnt * row, st), "hipMemsetAsync (gradient rows staging)");
-        HIP_TRY(hipMemsetAsync(stage_g, 0, (size_t)cnt * row, st), "hipMemsetAsync (gradient rows staging)");
+        HIP_TRY(hipMemsetAsync(stage_z, 0, (size_t)cnt * row, st), memset_what);
+        if (grows) HIP_TRY(hipMemsetAsync(stage_g, 0, (size_t)cnt * row, st), memset_what);
         int rc = conv_impl<float>(x + lo * L * C, stage_z, stage_g, nullptr, radem, chi, seqlen_host + lo, seqlen_dev + lo, cnt, L, C, cnt,
-                                  num_rffs, cnt, num_rffs, num_freqs, R, cnt, sigma, conv_width, scaling_type, MODE_CONV_GRAD, workspace, off,
-                                  (void *)st);
+                                  num_rffs, cnt, num_rffs, num_freqs, R, cnt, sigma, conv_width, scaling_type,
+                                  grows ? MODE_CONV_GRAD : MODE_CONV, workspace, off, (void *)st);
         if (rc) return rc;
         // KernelBase.gradient_x: xgrad[:, 0] = 0 under an intercept (the rounding pass below writes the 1.0f of the features itself)
-        if (fit_intercept)
+        if (grows && fit_intercept)
             HIP_TRY(hipMemset2DAsync(stage_g, row, 0, sizeof(double), (size_t)cnt, st), "hipMemset2DAsync (gradient rows staging)");
         const long npairs = cnt * (num_rffs / 2);
         const long nblocks = (npairs + 255) / 256;
         if (nblocks > 2147483647L) return fail(XGPR_ERR_UNSUPPORTED, "staging slice too large for one rounding launch");
-        hipLaunchKernelGGL(round_rows_kernel, dim3((unsigned)nblocks), dim3(256), 0, st, reinterpret_cast<const double2 *>(stage_z),
-                           reinterpret_cast<float2 *>(zrows + lo * num_rffs), npairs, num_rffs / 2, fit_intercept);
-        HIP_TRY(hipGetLastError(), "round_rows_kernel launch");
-        hipLaunchKernelGGL(round_rows_kernel, dim3((unsigned)nblocks), dim3(256), 0, st, reinterpret_cast<const double2 *>(stage_g),
-                           reinterpret_cast<float2 *>(grows + lo * num_rffs), npairs, num_rffs / 2, 0);
-        HIP_TRY(hipGetLastError(), "round_rows_kernel launch");
+        rc = launch(round_rows_kernel, dim3((unsigned)nblocks), dim3(256), 0, st, "round_rows_kernel launch",
+                    reinterpret_cast<const double2 *>(stage_z), reinterpret_cast<float2 *>(zrows + lo * num_rffs), npairs, num_rffs / 2, fit_intercept);
+        if (rc) return rc;
+        if (grows) {
+            rc = launch(round_rows_kernel, dim3((unsigned)nblocks), dim3(256), 0, st, "round_rows_kernel launch",
+                        reinterpret_cast<const double2 *>(stage_g), reinterpret_cast<float2 *>(grows + lo * num_rffs), npairs, num_rffs / 2, 0);
+            if (rc) return rc;
+        }
     }
     return 0;
 }
@@ -617,10 +580,8 @@ int ztz_impl(const float *x, const int8_t *radem, const float *chi, const double
              long d, long num_rffs, long num_freqs, long R, int fit_intercept, void *workspace, size_t wbytes,
              void *stream) {
     const long P = padded_width(d);
-    if (n == 0) return fail(XGPR_ERR_NO_DATAPOINTS, "no datapoints");
-    if (num_rffs < 2 || (num_rffs & 1) != 0) return fail(XGPR_ERR_ODD_OUTPUT, "last dim of output must be even number");
-    if (2 * num_freqs != num_rffs || num_freqs > R) return fail(XGPR_ERR_RFFS_FREQS, "incorrect number of rffs and or freqs.");
-    if (R % P != 0) return fail(XGPR_ERR_RFFS_FREQS, "incorrect number of rffs and or freqs.");
+    int rc = check_sorf_shape(n, num_rffs, num_freqs, R, P);
+    if (rc) return rc;
     if (P > 4096) return fail(XGPR_ERR_UNSUPPORTED, "fused matvec supports padded width <= 4096");
     if (num_freqs > 65536) return fail(XGPR_ERR_UNSUPPORTED, "fused matvec supports num_freqs <= 65536");
     if ((MATVEC && !aligned16(vec)) || !aligned16(w_out)) return fail(XGPR_ERR_WORKSPACE, "vector pointers must be 16-byte aligned");
@@ -632,11 +593,9 @@ int ztz_impl(const float *x, const int8_t *radem, const float *chi, const double
     if (MATVEC && ztz_takes_two_passes(d, P, num_freqs, aligned16(x)))
         return ztz_two_pass(x, radem, chi, vec, w_out, n, d, num_rffs, num_freqs, R, fit_intercept, workspace, st);
 
-    WaveArgs a = {};
-    a.x = x; a.masks = (const uint64_t *)workspace; a.chi = chi; a.vec = vec;
+    WaveArgs a = wave_args(x, chi, workspace, n, d, d, num_freqs, R);
+    a.vec = vec;
     a.wpart = reinterpret_cast<double *>(reinterpret_cast<unsigned char *>(workspace) + mb);
-    a.n = n; a.row_stride = d; a.F = num_freqs; a.d = (int)d;
-    a.MW = masks_per_diag(R); a.nb = (int)((num_freqs + 1023) / 1024);
     // 8 waves per workgroup where possible (2 per SIMD, the register budget of this kernel): the
     // G datapoint slots of a workgroup share one copy of v in LDS
     a.G = a.nb >= 8 ? 1 : 8 / a.nb;
@@ -644,8 +603,7 @@ int ztz_impl(const float *x, const int8_t *radem, const float *chi, const double
     a.fit_intercept = fit_intercept;
     a.scale = rbf_scale<float>(num_freqs, fit_intercept);
     const int lg = ilog2(P);
-    fill_norms(a, lg);
-    int rc = radem ? pack_masks(radem, (uint64_t *)workspace, R, a.MW, st) : 0;   // NULL: masks already in the workspace
+    rc = radem ? pack_masks(radem, (uint64_t *)workspace, R, a.MW, st) : 0;   // NULL: masks already in the workspace
     if (rc) return rc;
 
     // the three-waves-per-SIMD kernel (fused_ztz.inc) wherever its shape conditions hold, for the matvec and for
@@ -675,21 +633,11 @@ int ztz_impl(const float *x, const int8_t *radem, const float *chi, const double
         if (nblocks3 > by_rows) nblocks3 = by_rows;
         if (nblocks3 * a.G > ZTZ_MAX_SLABS) nblocks3 = ZTZ_MAX_SLABS / a.G;
         const size_t lds3 = ztz3_lds_bytes(a.nb, P);
-#define CALL_ZTZ3(LG)                                                                                        \
-        if constexpr (LG >= 1) {                                                                             \
-            auto kern = a.dma1 ? ztz3_kernel<LG, MATVEC ? Z3_MATVEC : Z3_ZTY, true>                          \
-                               : ztz3_kernel<LG, MATVEC ? Z3_MATVEC : Z3_ZTY, false>;                        \
-            int rc3 = allow_big_lds(kern, lds3);                                                             \
-            if (rc3) return rc3;                                                                             \
-            hipLaunchKernelGGL(kern, dim3((unsigned)nblocks3, (unsigned)ngroups3), dim3(z3_waves(LG) * 64), lds3, st, a); \
-        }
-        DISPATCH_LOG2P_Z3(lg, CALL_ZTZ3)
-#undef CALL_ZTZ3
-        HIP_TRY(hipGetLastError(), "ztz3_kernel launch");
-        hipLaunchKernelGGL(reduce_slabs_kernel, dim3((unsigned)((num_rffs + 63) / 64)), dim3(256), 0, st, a.wpart, w_out,
-                           num_rffs, nblocks3);         // one slab per workgroup (its G slots are added up in LDS)
-        HIP_TRY(hipGetLastError(), "reduce_slabs_kernel launch");
-        return 0;
+        rc = dispatch_lg<1, 12>(lg, TOO_WIDE_Z3, [&](auto LG) {
+            return launch_ztz3<decltype(LG)::value, MATVEC ? Z3_MATVEC : Z3_ZTY>(a, nblocks3, ngroups3, lds3, st, "ztz3_kernel launch");
+        });
+        if (rc) return rc;
+        return reduce_slabs(a.wpart, w_out, num_rffs, nblocks3, st);         // one slab per workgroup (its G slots are added up in LDS)
     }
 
     if (wide) return fail(XGPR_ERR_UNSUPPORTED, "fused matvec: no plan for this shape at padded width > 1024");
@@ -711,25 +659,14 @@ int ztz_impl(const float *x, const int8_t *radem, const float *chi, const double
     // the two-layout FHT needs 5 KiB of LDS per wave; without room for it (M = 16384) the register-only FHT runs
     const bool tp = lg >= 7 && lds_t * wg_per_cu <= 160 * 1024;
     const size_t lds = tp ? lds_t : lds_base;
-#define CALL_ZTZ(LG)                                                                                        \
-    if (tp) {                                                                                               \
-        auto kern = wave_ztz_kernel<LG, MATVEC, true>;                                                      \
-        int rc2 = allow_big_lds(kern, lds);                                                                 \
-        if (rc2) return rc2;                                                                                \
-        hipLaunchKernelGGL(kern, dim3((unsigned)nblocks), dim3(waves_per_wg * 64), lds, st, a);            \
-    } else {                                                                                                \
-        auto kern = wave_ztz_kernel<LG, MATVEC, false>;                                                     \
-        int rc2 = allow_big_lds(kern, lds);                                                                 \
-        if (rc2) return rc2;                                                                                \
-        hipLaunchKernelGGL(kern, dim3((unsigned)nblocks), dim3(waves_per_wg * 64), lds, st, a);            \
-    }
-    DISPATCH_LOG2P(lg, CALL_ZTZ)
-#undef CALL_ZTZ
-    HIP_TRY(hipGetLastError(), "wave_ztz_kernel launch");
-    hipLaunchKernelGGL(reduce_slabs_kernel, dim3((unsigned)((num_rffs + 63) / 64)), dim3(256), 0, st, a.wpart, w_out,
-                       num_rffs, nslabs);
-    HIP_TRY(hipGetLastError(), "reduce_slabs_kernel launch");
-    return 0;
+    rc = dispatch_lg<1, 10>(lg, TOO_WIDE_WAVE, [&](auto LG) {
+        return dispatch_bool(tp, [&](auto TP) {
+            return launch(wave_ztz_kernel<decltype(LG)::value, MATVEC, decltype(TP)::value>, dim3((unsigned)nblocks), dim3(waves_per_wg * 64),
+                          lds, st, "wave_ztz_kernel launch", a);
+        });
+    });
+    if (rc) return rc;
+    return reduce_slabs(a.wpart, w_out, num_rffs, nslabs, st);
 }
 
 // Z^T(Z v) for more tiles per datapoint than one workgroup holds (ztz_takes_two_passes): per window of rows, (1) the dot
@@ -740,16 +677,13 @@ int ztz_two_pass(const float *x, const int8_t *radem, const float *chi, const do
                  long d, long num_rffs, long num_freqs, long R, int fit_intercept, void *workspace, hipStream_t st) {
     const long P = padded_width(d);
     const size_t mb = masks_bytes(R);
-    WaveArgs a = {};
-    a.masks = (const uint64_t *)workspace; a.chi = chi; a.vec = vec;
+    WaveArgs a = wave_args(x, chi, workspace, n, d, d, num_freqs, R);       // (x and n: per row window, below)
+    a.vec = vec;
     a.wpart = reinterpret_cast<double *>(reinterpret_cast<unsigned char *>(workspace) + mb);
     a.tpart = a.wpart + (size_t)ZTZ_MAX_SLABS * num_rffs;
-    a.row_stride = d; a.F = num_freqs; a.d = (int)d;
-    a.MW = masks_per_diag(R); a.nb = (int)((num_freqs + 1023) / 1024);
     a.G = 1; a.fit_intercept = fit_intercept;
     a.scale = rbf_scale<float>(num_freqs, fit_intercept);
     const int lg = ilog2(P);
-    fill_norms(a, lg);
     int rc = radem ? pack_masks(radem, (uint64_t *)workspace, R, a.MW, st) : 0;   // NULL: masks already in the workspace
     if (rc) return rc;
     // the three-wave plan (fused_ztz.inc, Z3_DOT / Z3_UPD): workgroups of 12 waves = slots x a group of `nbg` consecutive
@@ -771,36 +705,20 @@ int ztz_two_pass(const float *x, const int8_t *radem, const float *chi, const do
         a.dma1 = ztz3_dma1(a.x, d);
         a.n = rows;
         a.add_to_slab = row0 > 0;
-#define CALL_Z3P(LG, MODE_)                                                                                   \
-        if constexpr (LG >= 1) {                                                                         \
-            auto kern = a.dma1 ? ztz3_kernel<LG, MODE_, true> : ztz3_kernel<LG, MODE_, false>;           \
-            int rc3 = allow_big_lds(kern, lds3);                                                         \
-            if (rc3) return rc3;                                                                         \
-            hipLaunchKernelGGL(kern, dim3((unsigned)ncols, (unsigned)ngroups), dim3(z3_waves(LG) * 64), lds3, st, a);  \
-        }
-#define CALL_Z3DOT(LG) CALL_Z3P(LG, Z3_DOT)
-#define CALL_Z3UPD(LG) CALL_Z3P(LG, Z3_UPD)
-        DISPATCH_LOG2P_Z3(lg, CALL_Z3DOT)
-        HIP_TRY(hipGetLastError(), "ztz3_kernel (dot pass) launch");
-        DISPATCH_LOG2P_Z3(lg, CALL_Z3UPD)
-        HIP_TRY(hipGetLastError(), "ztz3_kernel (update pass) launch");
-#undef CALL_Z3DOT
-#undef CALL_Z3UPD
-#undef CALL_Z3P
+        rc = dispatch_lg<1, 12>(lg, TOO_WIDE_Z3, [&](auto LG) {
+            const int rcd = launch_ztz3<decltype(LG)::value, Z3_DOT>(a, ncols, ngroups, lds3, st, "ztz3_kernel (dot pass) launch");
+            return rcd ? rcd : launch_ztz3<decltype(LG)::value, Z3_UPD>(a, ncols, ngroups, lds3, st, "ztz3_kernel (update pass) launch");
+        });
+        if (rc) return rc;
     }
-    hipLaunchKernelGGL(reduce_slabs_kernel, dim3((unsigned)((num_rffs + 63) / 64)), dim3(256), 0, st, a.wpart, w_out,
-                       num_rffs, ncols);
-    HIP_TRY(hipGetLastError(), "reduce_slabs_kernel launch");
-    return 0;
+    return reduce_slabs(a.wpart, w_out, num_rffs, ncols, st);
 }
 
 int zcache_build_impl(const float *x, float *zc, const int8_t *radem, const float *chi, long n, long d,
                       long num_rffs, long num_freqs, long R, void *workspace, size_t wbytes, void *stream) {
     const long P = padded_width(d);
-    if (n == 0) return fail(XGPR_ERR_NO_DATAPOINTS, "no datapoints");
-    if (num_rffs < 2 || (num_rffs & 1) != 0) return fail(XGPR_ERR_ODD_OUTPUT, "last dim of output must be even number");
-    if (2 * num_freqs != num_rffs || num_freqs > R) return fail(XGPR_ERR_RFFS_FREQS, "incorrect number of rffs and or freqs.");
-    if (R % P != 0) return fail(XGPR_ERR_RFFS_FREQS, "incorrect number of rffs and or freqs.");
+    int rc = check_sorf_shape(n, num_rffs, num_freqs, R, P);
+    if (rc) return rc;
     if (!workspace || wbytes < masks_bytes(R)) return fail(XGPR_ERR_WORKSPACE, "workspace too small (see xgpr_rbf_workspace_bytes)");
     if ((reinterpret_cast<uintptr_t>(zc) & 7) != 0) return fail(XGPR_ERR_WORKSPACE, "cache pointer must be 8-byte aligned");
     hipStream_t st = (hipStream_t)stream;
@@ -809,10 +727,8 @@ int zcache_build_impl(const float *x, float *zc, const int8_t *radem, const floa
         // conditions, the any-width path otherwise (in LDS up to 32768 floats, beyond that in the workspace's global scratch:
         // xgpr_sorf_workspace_bytes)
         if (d > 2147483647L) return fail(XGPR_ERR_UNSUPPORTED, "the feature cache: input width beyond 2^31 - 1");
-        SorfArgs<float> s = {};
-        s.x = x; s.outf = zc; s.radem = radem; s.chi = chi;
-        s.n = n; s.row_stride = d; s.F = num_freqs; s.R = R; s.d = (int)d;
-        s.P = (int)P; s.reps = (int)((num_freqs + P - 1) / P); s.nc = norm_constant<float>(P);
+        SorfArgs<float> s = sorf_args(x, radem, chi, n, d, d, num_freqs, R);
+        s.outf = zc;
         if (P == 8192 && !wave_tile_plan_off() && R % 64 == 0 && (reinterpret_cast<uintptr_t>(radem) & 15) == 0) {
             using WT = WaveTile<float, 13>;
             return launch_wave_tile(wave_tile_rbf_cache_kernel<13>, s, n * (R / 1024), WT::WAVES, WT::LDS_BYTES, st,
@@ -820,13 +736,10 @@ int zcache_build_impl(const float *x, float *zc, const int8_t *radem, const floa
         }
         return launch_generic_sorf<float, MODE_RBF_CACHE>(s, workspace, wbytes, st);
     }
-    WaveArgs a = {};
-    a.x = x; a.outf = zc; a.masks = (const uint64_t *)workspace; a.chi = chi;
-    a.n = n; a.row_stride = d; a.F = num_freqs; a.d = (int)d;
-    a.MW = masks_per_diag(R); a.nb = (int)((num_freqs + 1023) / 1024);
+    WaveArgs a = wave_args(x, chi, workspace, n, d, d, num_freqs, R);
+    a.outf = zc;
     const int lg = ilog2(P);
-    fill_norms(a, lg);
-    int rc = pack_masks(radem, (uint64_t *)workspace, R, a.MW, st);
+    rc = pack_masks(radem, (uint64_t *)workspace, R, a.MW, st);
     if (rc) return rc;
     {
         const int rcf = launch_ztz3_feat<Z3_FEAT32>(a, P, lg, st);
@@ -835,11 +748,9 @@ int zcache_build_impl(const float *x, float *zc, const int8_t *radem, const floa
     if (P > 1024) return fail(XGPR_ERR_UNSUPPORTED, "the feature cache: no plan for this shape at padded width > 1024");
     const long nblocks = (n * a.nb + 3) / 4;
     if (nblocks > 2147483647L) return fail(XGPR_ERR_UNSUPPORTED, "too many datapoints for one launch");
-#define CALL_RBFC(LG) hipLaunchKernelGGL((wave_rbf_kernel<LG, OUT_CACHE>), dim3((unsigned)nblocks), dim3(256), 0, st, a)
-    DISPATCH_LOG2P(lg, CALL_RBFC)
-#undef CALL_RBFC
-    HIP_TRY(hipGetLastError(), "wave_rbf_kernel (cache) launch");
-    return 0;
+    return dispatch_lg<1, 10>(lg, TOO_WIDE_WAVE, [&](auto LG) {
+        return launch(wave_rbf_kernel<decltype(LG)::value, OUT_CACHE>, dim3((unsigned)nblocks), dim3(256), 0, st, "wave_rbf_kernel (cache) launch", a);
+    });
 }
 
 // ---- float32 feature AND gradient rows of the fixed-vector kernels (xgpr_rbf_grad_rows_f32): the float32 gradient operator's kernels
@@ -849,48 +760,39 @@ int rbf_grad_rows_impl(const float *x, float *zrows, float *grows, const int8_t 
                        long num_rffs, long num_freqs, long R, double sigma, int fit_intercept, void *workspace, size_t wbytes,
                        void *stream) {
     const long P = padded_width(d);
-    if (n == 0) return fail(XGPR_ERR_NO_DATAPOINTS, "no datapoints");
-    if (num_rffs < 2 || (num_rffs & 1) != 0) return fail(XGPR_ERR_ODD_OUTPUT, "last dim of output must be even number");
-    if (2 * num_freqs != num_rffs || num_freqs > R) return fail(XGPR_ERR_RFFS_FREQS, "incorrect number of rffs and or freqs.");
-    if (R % P != 0) return fail(XGPR_ERR_RFFS_FREQS, "incorrect number of rffs and or freqs.");
+    int rc = check_sorf_shape(n, num_rffs, num_freqs, R, P);
+    if (rc) return rc;
     if (P > 8192) return fail(XGPR_ERR_UNSUPPORTED, "the gradient rows: no plan at padded width > 8192");
     if (!zrows || !grows || (reinterpret_cast<uintptr_t>(zrows) & 7) != 0 || (reinterpret_cast<uintptr_t>(grows) & 7) != 0)
         return fail(XGPR_ERR_WORKSPACE, "row pointers must be 8-byte aligned");
     hipStream_t st = (hipStream_t)stream;
-    // rbf_ops.cpp:180-185: a double constant in the gradient op
-    const double scale = fit_intercept ? sqrt(1.0 / ((double)num_freqs - 0.5)) : sqrt(1.0 / (double)num_freqs);
+    const double scale = rbf_scale<double>(num_freqs, fit_intercept);
+    const int lg = ilog2(P);
     if (P <= 1024) {
         if (!workspace || wbytes < masks_bytes(R)) return fail(XGPR_ERR_WORKSPACE, "workspace too small (see xgpr_rbf_workspace_bytes)");
-        WaveArgs a = {};
-        a.x = x; a.outf = zrows; a.gradf = grows; a.masks = (const uint64_t *)workspace; a.chi = chi;
-        a.n = n; a.row_stride = d; a.F = num_freqs; a.d = (int)d;
-        a.MW = masks_per_diag(R); a.nb = (int)((num_freqs + 1023) / 1024);
+        WaveArgs a = wave_args(x, chi, workspace, n, d, d, num_freqs, R);
+        a.outf = zrows; a.gradf = grows;
         a.scale = scale; a.sigma = sigma; a.fit_intercept = fit_intercept;
-        const int lg = ilog2(P);
-        fill_norms(a, lg);
         const long nblocks = (n * a.nb + 3) / 4;
         if (nblocks > 2147483647L) return fail(XGPR_ERR_UNSUPPORTED, "too many datapoints for one launch");
-        int rc = pack_masks(radem, (uint64_t *)workspace, R, a.MW, st);
+        rc = pack_masks(radem, (uint64_t *)workspace, R, a.MW, st);
         if (rc) return rc;
-#define CALL_RBFGR(LG) hipLaunchKernelGGL((wave_rbf_kernel<LG, OUT_GRAD_ROWS>), dim3((unsigned)nblocks), dim3(256), 0, st, a)
-        DISPATCH_LOG2P(lg, CALL_RBFGR)
-#undef CALL_RBFGR
-        HIP_TRY(hipGetLastError(), "wave_rbf_kernel (gradient rows) launch");
-        return 0;
+        return dispatch_lg<1, 10>(lg, TOO_WIDE_WAVE, [&](auto LG) {
+            return launch(wave_rbf_kernel<decltype(LG)::value, OUT_GRAD_ROWS>, dim3((unsigned)nblocks), dim3(256), 0, st,
+                          "wave_rbf_kernel (gradient rows) launch", a);
+        });
     }
     if (R % 64 != 0 || (reinterpret_cast<uintptr_t>(radem) & 15) != 0)
         return fail(XGPR_ERR_UNSUPPORTED, "the gradient rows: the wave tiles read the Rademacher array 16 bytes at a time");
-    SorfArgs<float> s = {};
-    s.x = x; s.outf = zrows; s.gradf = grows; s.radem = radem; s.chi = chi;
-    s.n = n; s.row_stride = d; s.F = num_freqs; s.R = R; s.d = (int)d;
-    s.P = (int)P; s.reps = (int)((num_freqs + P - 1) / P); s.nc = norm_constant<float>(P);
+    SorfArgs<float> s = sorf_args(x, radem, chi, n, d, d, num_freqs, R);
+    s.outf = zrows; s.gradf = grows;
     s.sigma = sigma; s.scale = scale; s.fit_intercept = fit_intercept;
     const long items = n * (R / 1024);
-    switch (ilog2(P)) {
-        case 11: return launch_wave_tile(wave_tile_rbf_grad_rows_kernel<11>, s, items, WaveTile<float, 11>::WAVES, WaveTile<float, 11>::LDS_BYTES, st, "wave_tile_rbf_grad_rows_kernel launch");
-        case 12: return launch_wave_tile(wave_tile_rbf_grad_rows_kernel<12>, s, items, WaveTile<float, 12>::WAVES, WaveTile<float, 12>::LDS_BYTES, st, "wave_tile_rbf_grad_rows_kernel launch");
-        default: return launch_wave_tile(wave_tile_rbf_grad_rows_kernel<13>, s, items, WaveTile<float, 13>::WAVES, WaveTile<float, 13>::LDS_BYTES, st, "wave_tile_rbf_grad_rows_kernel launch");
-    }
+    return dispatch_lg<11, 13>(lg, TOO_WIDE_WT, [&](auto LGc) {
+        using WT = WaveTile<float, decltype(LGc)::value>;
+        return launch_wave_tile(wave_tile_rbf_grad_rows_kernel<decltype(LGc)::value>, s, items, WT::WAVES, WT::LDS_BYTES, st,
+                                "wave_tile_rbf_grad_rows_kernel launch");
+    });
 }
 
 int zcache_matvec_impl(const float *zc, const double *vec, double *w_out, long n, long num_rffs, int fit_intercept,
@@ -919,22 +821,10 @@ int zcache_matvec_impl(const float *zc, const double *vec, double *w_out, long n
         if (nwg > n) nwg = n;
         if (nwg > ZTZ_MAX_SLABS) nwg = ZTZ_MAX_SLABS;
         const size_t wlds = (size_t)8 * 1024 * 16 + 2 * 8 * sizeof(double);
-        if (F % 2 == 0) {
-            auto kern = zcache_ztz_wide_kernel<true>;
-            int rc = allow_big_lds(kern, wlds);
-            if (rc) return rc;
-            hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3(512), wlds, st, a);
-        } else {
-            auto kern = zcache_ztz_wide_kernel<false>;
-            int rc = allow_big_lds(kern, wlds);
-            if (rc) return rc;
-            hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3(512), wlds, st, a);
-        }
-        HIP_TRY(hipGetLastError(), "zcache_ztz_wide_kernel launch");
-        hipLaunchKernelGGL(reduce_slabs_kernel, dim3((unsigned)((num_rffs + 63) / 64)), dim3(256), 0, st, a.wpart, w_out,
-                           num_rffs, nwg);
-        HIP_TRY(hipGetLastError(), "reduce_slabs_kernel launch");
-        return 0;
+        const int rc = dispatch_bool(F % 2 == 0, [&](auto EVEN) {
+            return launch(zcache_ztz_wide_kernel<decltype(EVEN)::value>, dim3((unsigned)nwg), dim3(512), wlds, st, "zcache_ztz_wide_kernel launch", a);
+        });
+        return rc ? rc : reduce_slabs(a.wpart, w_out, num_rffs, nwg, st);
     }
     const int waves = a.nb * a.G;
     long nblocks = device_cus();
@@ -943,22 +833,10 @@ int zcache_matvec_impl(const float *zc, const double *vec, double *w_out, long n
     if (nblocks * a.G > ZTZ_MAX_SLABS) nblocks = ZTZ_MAX_SLABS / a.G;
     constexpr int RING = 2;     // measured: 6.3 TB/s with 2 (222 VGPRs), 6.0 with 3, 3.8 with 4 (spills)
     const size_t lds = (size_t)a.nb * 1024 * 16 + 2 * 8 * 8 * sizeof(double);
-    if (F % 2 == 0) {
-        auto kern = zcache_ztz_kernel<true, RING>;
-        int rc = allow_big_lds(kern, lds);
-        if (rc) return rc;
-        hipLaunchKernelGGL(kern, dim3((unsigned)nblocks), dim3(waves * 64), lds, st, a);
-    } else {
-        auto kern = zcache_ztz_kernel<false, RING>;
-        int rc = allow_big_lds(kern, lds);
-        if (rc) return rc;
-        hipLaunchKernelGGL(kern, dim3((unsigned)nblocks), dim3(waves * 64), lds, st, a);
-    }
-    HIP_TRY(hipGetLastError(), "zcache_ztz_kernel launch");
-    hipLaunchKernelGGL(reduce_slabs_kernel, dim3((unsigned)((num_rffs + 63) / 64)), dim3(256), 0, st, a.wpart, w_out,
-                       num_rffs, nblocks * a.G);
-    HIP_TRY(hipGetLastError(), "reduce_slabs_kernel launch");
-    return 0;
+    const int rc = dispatch_bool(F % 2 == 0, [&](auto EVEN) {
+        return launch(zcache_ztz_kernel<decltype(EVEN)::value, RING>, dim3((unsigned)nblocks), dim3(waves * 64), lds, st, "zcache_ztz_kernel launch", a);
+    });
+    return rc ? rc : reduce_slabs(a.wpart, w_out, num_rffs, nblocks * a.G, st);
 }
 
 // z^T y over float32 feature rows (xgpr_zcache_zty_f32): ~8 workgroups per CU of 512 columns x a contiguous range of rows, partial
@@ -983,12 +861,9 @@ int zcache_zty_impl(const float *zc, const double *y, double *out, long n, long 
     const long rows_per_slab = (n + nslabs - 1) / nslabs;
     nslabs = (n + rows_per_slab - 1) / rows_per_slab;
     double *wpart = reinterpret_cast<double *>(workspace);
-    hipLaunchKernelGGL(zcache_zty_kernel, dim3((unsigned)ncb, (unsigned)nslabs), dim3(256), 0, st, zc, y, wpart, n, num_rffs,
-                       rows_per_slab, fit_intercept, scale);
-    HIP_TRY(hipGetLastError(), "zcache_zty_kernel launch");
-    hipLaunchKernelGGL(reduce_slabs_kernel, dim3((unsigned)((num_rffs + 63) / 64)), dim3(256), 0, st, wpart, out, num_rffs, nslabs);
-    HIP_TRY(hipGetLastError(), "reduce_slabs_kernel launch");
-    return 0;
+    const int rc = launch(zcache_zty_kernel, dim3((unsigned)ncb, (unsigned)nslabs), dim3(256), 0, st, "zcache_zty_kernel launch", zc, y, wpart,
+                          n, num_rffs, rows_per_slab, fit_intercept, scale);
+    return rc ? rc : reduce_slabs(wpart, out, num_rffs, nslabs, st);
 }
 
 struct ZbGeom { int kp; long mblk; long nrb; long rows_per_range; size_t t_bytes; size_t slab_bytes;
@@ -1166,18 +1041,10 @@ int srht_sample_impl(const T *z, const int8_t *radem, const long *sampler, T *ou
         part = reinterpret_cast<double *>(workspace);
     }
     hipStream_t st = (hipStream_t)stream;
-    const size_t lds = (size_t)P * sizeof(T);
-    auto kern = srht_sample_kernel<T>;
-    int rc = allow_big_lds(kern, lds);
-    if (rc) return rc;
-    hipLaunchKernelGGL(kern, dim3((unsigned)nblocks), dim3(nt), lds, st, z, radem, sampler, out, y, part, n, m, (int)P, ncols,
-                       ldo, norm_constant<T>(P));
-    HIP_TRY(hipGetLastError(), "srht_sample_kernel launch");
-    if (y) {
-        hipLaunchKernelGGL(reduce_slabs_kernel, dim3((unsigned)((m + 63) / 64)), dim3(256), 0, st, part, zty_out, m, nblocks);
-        HIP_TRY(hipGetLastError(), "reduce_slabs_kernel launch");
-    }
-    return 0;
+    const int rc = launch(srht_sample_kernel<T>, dim3((unsigned)nblocks), dim3(nt), (size_t)P * sizeof(T), st, "srht_sample_kernel launch", z,
+                          radem, sampler, out, y, part, n, m, (int)P, ncols, ldo, norm_constant<T>(P));
+    if (rc || !y) return rc;
+    return reduce_slabs(part, zty_out, m, nblocks, st);
 }
 
 
@@ -1216,22 +1083,13 @@ int srht_sample_rows_impl(const float *zc, const int8_t *radem, const long *samp
         long nb16 = (lds16 * 2 <= 160 * 1024 ? 2L : 1L) * device_cus();
         if (nb16 > n) nb16 = n;
         if (nb16 > SRHT_ZTY_MAX_BLOCKS) nb16 = SRHT_ZTY_MAX_BLOCKS;
-#define SRHT16_LAUNCH(LG)                                                                                         \
-        {                                                                                                         \
-            auto kern = srht_sample_rows16_kernel<LG>;                                                            \
-            int rc = allow_big_lds(kern, lds16);                                                                  \
-            if (rc) return rc;                                                                                    \
-            hipLaunchKernelGGL(kern, dim3((unsigned)nb16), dim3((unsigned)(P / 16)), lds16, st, zc, radem, sampler, out, y,   \
-                               part, n, m, ncols, ldo, nc, scale, fit_intercept);                                 \
-        }
-        if (P == 4096) SRHT16_LAUNCH(12) else SRHT16_LAUNCH(13)
-#undef SRHT16_LAUNCH
-        HIP_TRY(hipGetLastError(), "srht_sample_rows16_kernel launch");
-        if (y) {
-            hipLaunchKernelGGL(reduce_slabs_kernel, dim3((unsigned)((m + 63) / 64)), dim3(256), 0, st, part, zty_out, m, nb16);
-            HIP_TRY(hipGetLastError(), "reduce_slabs_kernel launch");
-        }
-        return 0;
+        auto go = [&](auto kern) {
+            return launch(kern, dim3((unsigned)nb16), dim3((unsigned)(P / 16)), lds16, st, "srht_sample_rows16_kernel launch", zc, radem, sampler,
+                          out, y, part, n, m, ncols, ldo, nc, scale, fit_intercept);
+        };
+        const int rc = P == 4096 ? go(srht_sample_rows16_kernel<12>) : go(srht_sample_rows16_kernel<13>);
+        if (rc || !y) return rc;
+        return reduce_slabs(part, zty_out, m, nb16, st);
     }
     // rows of 2 or 4 blocks of 8192 with at most 2048 sampled columns: the register passes block by block
     const bool blocks16 = NB > 1 && !no16 && PB == 8192 && ldo <= 2048 && m % 4 == 0 && aligned16(zc) && aligned16(radem);
@@ -1239,30 +1097,19 @@ int srht_sample_rows_impl(const float *zc, const int8_t *radem, const long *samp
         const size_t lds16 = (size_t)(PB / 16 + PB / 256) * 16 * sizeof(double);
         long nb16 = 2L * device_cus();
         if (nb16 > n) nb16 = n;
-        if (NB == 2) {
-            auto kern = srht_sample_rows16_blocks_kernel<2>;
-            int rc = allow_big_lds(kern, lds16);
-            if (rc) return rc;
-            hipLaunchKernelGGL(kern, dim3((unsigned)nb16), dim3(512), lds16, st, zc, radem, sampler, out, n, m, ncols, ldo, nc, scale, fit_intercept);
-        } else {
-            auto kern = srht_sample_rows16_blocks_kernel<4>;
-            int rc = allow_big_lds(kern, lds16);
-            if (rc) return rc;
-            hipLaunchKernelGGL(kern, dim3((unsigned)nb16), dim3(512), lds16, st, zc, radem, sampler, out, n, m, ncols, ldo, nc, scale, fit_intercept);
-        }
-        HIP_TRY(hipGetLastError(), "srht_sample_rows16_blocks_kernel launch");
+        auto go = [&](auto kern) {
+            return launch(kern, dim3((unsigned)nb16), dim3(512), lds16, st, "srht_sample_rows16_blocks_kernel launch", zc, radem, sampler, out, n, m,
+                          ncols, ldo, nc, scale, fit_intercept);
+        };
+        const int rc = NB == 2 ? go(srht_sample_rows16_blocks_kernel<2>) : go(srht_sample_rows16_blocks_kernel<4>);
+        if (rc) return rc;
     } else {
-#define SRHT_ROWS_LAUNCH(NBV)                                                                                     \
-    {                                                                                                             \
-        auto kern = srht_sample_rows_kernel<NBV>;                                                                 \
-        int rc = allow_big_lds(kern, lds);                                                                        \
-        if (rc) return rc;                                                                                        \
-        hipLaunchKernelGGL(kern, dim3((unsigned)nblocks), dim3(nt), lds, st, zc, radem, sampler, out, y, part, n, m,   \
-                           (int)PB, ncols, ldo, nc, scale, fit_intercept);                                        \
-    }
-    if (NB == 1) SRHT_ROWS_LAUNCH(1) else if (NB == 2) SRHT_ROWS_LAUNCH(2) else SRHT_ROWS_LAUNCH(4)
-#undef SRHT_ROWS_LAUNCH
-    HIP_TRY(hipGetLastError(), "srht_sample_rows_kernel launch");
+        auto go = [&](auto kern) {
+            return launch(kern, dim3((unsigned)nblocks), dim3(nt), lds, st, "srht_sample_rows_kernel launch", zc, radem, sampler, out, y, part, n, m,
+                          (int)PB, ncols, ldo, nc, scale, fit_intercept);
+        };
+        const int rc = NB == 1 ? go(srht_sample_rows_kernel<1>) : NB == 2 ? go(srht_sample_rows_kernel<2>) : go(srht_sample_rows_kernel<4>);
+        if (rc) return rc;
     }
     if (y) {
         long nslabs = nblocks;
@@ -1276,8 +1123,7 @@ int srht_sample_rows_impl(const float *zc, const int8_t *radem, const long *samp
                                part, n, m, rpr, scale, fit_intercept);
             HIP_TRY(hipGetLastError(), "rows_zty_kernel launch");
         }
-        hipLaunchKernelGGL(reduce_slabs_kernel, dim3((unsigned)((m + 63) / 64)), dim3(256), 0, st, part, zty_out, m, nslabs);
-        HIP_TRY(hipGetLastError(), "reduce_slabs_kernel launch");
+        return reduce_slabs(part, zty_out, m, nslabs, st);
     }
     return 0;
 }
@@ -1361,18 +1207,10 @@ int sketch_gemm_impl(const double *A, long lda, const float *zc, long n, long nu
         SkArgs al = a;
         al.K = k16;
         if (gm.nsplit > 1 && K % 16 != 0) al.K = K / 16 * 16;       // ... except the end of the last one
-        if (trans_out) {
-            auto kern = sketch_gemm_lds_kernel<true>;
-            int rc = allow_big_lds(kern, 2 * SKL_BUF_BYTES);
-            if (rc) return rc;
-            hipLaunchKernelGGL(kern, grid, blk, 2 * SKL_BUF_BYTES, st, al);
-        } else {
-            auto kern = sketch_gemm_lds_kernel<false>;
-            int rc = allow_big_lds(kern, 2 * SKL_BUF_BYTES);
-            if (rc) return rc;
-            hipLaunchKernelGGL(kern, grid, blk, 2 * SKL_BUF_BYTES, st, al);
-        }
-        HIP_TRY(hipGetLastError(), "sketch_gemm_lds_kernel launch");
+        const int rc = dispatch_bool(trans_out != 0, [&](auto TR) {
+            return launch(sketch_gemm_lds_kernel<decltype(TR)::value>, grid, blk, 2 * SKL_BUF_BYTES, st, "sketch_gemm_lds_kernel launch", al);
+        });
+        if (rc) return rc;
         const long nrows_ = trans_out ? J : I, ncols_ = trans_out ? I : J;
         hipLaunchKernelGGL(sk_reduce_kernel, dim3((unsigned)((nrows_ * ncols_ + 255) / 256)), dim3(256), 0, st, a.C, C, nrows_,
                            ncols_, ldc, gm.slab_stride, (int)gm.nsplit, accumulate);
@@ -1386,26 +1224,14 @@ int sketch_gemm_impl(const double *A, long lda, const float *zc, long n, long nu
     // contract features: the LDS-staged form needs whole 16-feature chunks and a row pitch of Q that covers full tiles
     const bool lds_bt_ok = bt && !direct_only && lda % 128 == 0 && K % 16 == 0 && gm.k_per_split % 16 == 0 &&
                            num_rffs * 64 < 2147483647L;
-    if (lds_bt_ok) {
-        if (trans_out) {
-            auto kern = sketch_gemm_lds_bt_kernel<true>;
-            int rc = allow_big_lds(kern, 2 * SKB_BUF_BYTES);
-            if (rc) return rc;
-            hipLaunchKernelGGL(kern, grid, blk, 2 * SKB_BUF_BYTES, st, a);
-        } else {
-            auto kern = sketch_gemm_lds_bt_kernel<false>;
-            int rc = allow_big_lds(kern, 2 * SKB_BUF_BYTES);
-            if (rc) return rc;
-            hipLaunchKernelGGL(kern, grid, blk, 2 * SKB_BUF_BYTES, st, a);
-        }
-    } else if (bt) {
-        if (trans_out) hipLaunchKernelGGL((sketch_gemm_kernel<true, true>), grid, blk, 0, st, a);
-        else hipLaunchKernelGGL((sketch_gemm_kernel<true, false>), grid, blk, 0, st, a);
-    } else {
-        if (trans_out) hipLaunchKernelGGL((sketch_gemm_kernel<false, true>), grid, blk, 0, st, a);
-        else hipLaunchKernelGGL((sketch_gemm_kernel<false, false>), grid, blk, 0, st, a);
-    }
-    HIP_TRY(hipGetLastError(), "sketch_gemm_kernel launch");
+    // (all three forms report a failed launch under the same name)
+    const int rc = dispatch_bool(trans_out != 0, [&](auto TR) {
+        if (lds_bt_ok) return launch(sketch_gemm_lds_bt_kernel<decltype(TR)::value>, grid, blk, 2 * SKB_BUF_BYTES, st, "sketch_gemm_kernel launch", a);
+        return dispatch_bool(bt != 0, [&](auto BT) {
+            return launch(sketch_gemm_kernel<decltype(BT)::value, decltype(TR)::value>, grid, blk, 0, st, "sketch_gemm_kernel launch", a);
+        });
+    });
+    if (rc) return rc;
     const long nrows = trans_out ? J : I, ncols = trans_out ? I : J;
     hipLaunchKernelGGL(sk_reduce_kernel, dim3((unsigned)((nrows * ncols + 255) / 256)), dim3(256), 0, st, a.C, C, nrows, ncols,
                        ldc, gm.slab_stride, (int)gm.nsplit, accumulate);
@@ -1443,13 +1269,10 @@ int gram_impl(const float *zc, long n, long num_rffs, double *C, long ldc, long 
         long nwg = gram_workgroups(msub, n);
         a.units_per_wg = (total + nwg - 1) / nwg;
         nwg = (total + a.units_per_wg - 1) / a.units_per_wg;
-        auto kern = gram_lds_kernel;
-        int rc = allow_big_lds(kern, GR_LDS);
+        int rc = launch(gram_lds_kernel, dim3((unsigned)nwg), dim3(512), GR_LDS, st, "gram_lds_kernel launch", a);
         if (rc) return rc;
-        hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3(512), GR_LDS, st, a);
-        HIP_TRY(hipGetLastError(), "gram_lds_kernel launch");
-        hipLaunchKernelGGL(gram_fixup_kernel, dim3((unsigned)a.ntiles), dim3(256), 0, st, a, nwg);
-        HIP_TRY(hipGetLastError(), "gram_fixup_kernel launch");
+        rc = launch(gram_fixup_kernel, dim3((unsigned)a.ntiles), dim3(256), 0, st, "gram_fixup_kernel launch", a, nwg);
+        if (rc) return rc;
     } else if (!accumulate) {          // fewer rows than one chunk: the tail kernel adds into zeros (the padding columns stay untouched)
         HIP_TRY(hipMemset2DAsync(C, (size_t)ldc * sizeof(double), 0, (size_t)msub * sizeof(double), (size_t)msub, st), "gram: clearing C");
     }
@@ -1491,17 +1314,14 @@ int cross_gram_impl(const float *A, const float *B, long n, long num_rffs, doubl
         long nwg = cross_gram_workgroups(M, n);
         a.units_per_wg = (total + nwg - 1) / nwg;
         nwg = (total + a.units_per_wg - 1) / a.units_per_wg;
-        auto kern = cross_gram_lds_kernel;
-        int rc = allow_big_lds(kern, GR_LDS);
+        int rc = launch(cross_gram_lds_kernel, dim3((unsigned)nwg), dim3(512), GR_LDS, st, "cross_gram_lds_kernel launch", a);
         if (rc) return rc;
-        hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3(512), GR_LDS, st, a);
-        HIP_TRY(hipGetLastError(), "cross_gram_lds_kernel launch");
         // gram_fixup_kernel as it is: a tile here is a run of 2 nchunks units, its slabs are whole (mirrored) tiles
         GramArgs f = {};
         f.C = C; f.ldc = ldc; f.nchunks = 2 * a.nchunks; f.T = a.T; f.ntiles = a.ntiles; f.units_per_wg = a.units_per_wg;
         f.spill = a.spill;
-        hipLaunchKernelGGL(gram_fixup_kernel, dim3((unsigned)a.ntiles), dim3(256), 0, st, f, nwg);
-        HIP_TRY(hipGetLastError(), "gram_fixup_kernel (cross gram) launch");
+        rc = launch(gram_fixup_kernel, dim3((unsigned)a.ntiles), dim3(256), 0, st, "gram_fixup_kernel (cross gram) launch", f, nwg);
+        if (rc) return rc;
     } else if (!accumulate) {          // fewer rows than one chunk: the tail kernel adds into zeros
         HIP_TRY(hipMemset2DAsync(C, (size_t)ldc * sizeof(double), 0, (size_t)M * sizeof(double), (size_t)M, st), "cross gram: clearing C");
     }

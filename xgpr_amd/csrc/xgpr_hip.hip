@@ -29,6 +29,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <string>
+#include <type_traits>
 #include <dlfcn.h>
 #if __has_include(<rccl/rccl.h>)
 #include <rccl/rccl.h>          // types only: the library is resolved at run time (xgpr_rccl_load), never linked
@@ -167,7 +168,7 @@ int xgpr_conv1d_fgen_f64(const double *x, double *out, const int8_t *radem, cons
                              workspace, workspace_bytes, stream);
 }
 size_t xgpr_conv_feature_rows_workspace_bytes(long radem_shape2, long width, long num_rffs, long nseq) {
-    return conv_rows_workspace_bytes(radem_shape2, width, num_rffs, nseq);
+    return conv_rows_workspace_bytes(radem_shape2, width, num_rffs, nseq, 1);
 }
 int xgpr_conv_feature_rows_f32(const float *x, float *zc, const int8_t *radem, const float *chi,
                                const int32_t *seqlen_host, const int32_t *seqlen_dev, long n, long L, long C,
@@ -187,7 +188,7 @@ int xgpr_conv_grad_f32(const float *x, double *out, double *grad, const int8_t *
                             MODE_CONV_GRAD, workspace, workspace_bytes, stream);
 }
 size_t xgpr_conv_grad_rows_workspace_bytes(long radem_shape2, long width, long num_rffs, long nseq) {
-    return conv_grad_rows_workspace_bytes(radem_shape2, width, num_rffs, nseq);
+    return conv_rows_workspace_bytes(radem_shape2, width, num_rffs, nseq, 2);
 }
 int xgpr_conv_grad_rows_f32(const float *x, float *zrows, float *grows, const int8_t *radem, const float *chi,
                             const int32_t *seqlen_host, const int32_t *seqlen_dev, long n, long L, long C, long num_rffs,
@@ -308,10 +309,7 @@ int utr_block_launch(const double *u, const double *r, double *t_out, long M, lo
     if (k <= 16) hipLaunchKernelGGL((precond_utr_mfma_kernel<1>), grid, dim3(512), 0, st, u, r, part, M, rank, (int)k, gm.rows_per);
     else hipLaunchKernelGGL((precond_utr_mfma_kernel<2>), grid, dim3(512), 0, st, u, r, part, M, rank, (int)k, gm.rows_per);
     HIP_TRY(hipGetLastError(), "precond_utr_mfma_kernel launch");
-    const long total = rank * k;
-    hipLaunchKernelGGL(reduce_slabs_kernel, dim3((unsigned)((total + 63) / 64)), dim3(256), 0, st, part, t_out, total, gm.nrb);
-    HIP_TRY(hipGetLastError(), "reduce_slabs_kernel launch");
-    return 0;
+    return reduce_slabs(part, t_out, rank * k, gm.nrb, st);
 }
 }  // namespace
 size_t xgpr_precond_utr_block_workspace_bytes(long M, long rank, long k) {
