@@ -205,6 +205,31 @@ int xgpr_conv_grad_rows_f32(const float *x, float *zrows, float *grows, const in
                             long nseq, double sigma, int conv_width, int scaling_type, int fit_intercept,
                             void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- token-indexed input for the two float32 row writers above (no counterpart in the reference, which takes dense
+ * arrays only: these replace "expand table[tokens] to float32 [n, L, C] on the host, then xgpr_conv_feature_rows_f32 /
+ * xgpr_conv_grad_rows_f32").  tokens[n, L] (uint8, row-major) index the rows of table[vocab, C] (float32, row-major, vocab
+ * 1 .. 256); element e of the window of k-mer j is table[tokens[i, j + e / C]][e % C].  For the feature rows the table is
+ * already multiplied by sigma, for the gradient rows it is not -- as x is for the dense siblings.  Every other argument,
+ * the row format, the workspace (xgpr_conv_feature_rows_workspace_bytes / xgpr_conv_grad_rows_workspace_bytes with width =
+ * conv_width * C) and the error codes are the siblings'; the rows are BIT-IDENTICAL to the siblings' on the expanded array
+ * (same kernel body after the window fetch).  Token values must be < vocab (not checked on the device); positions beyond a
+ * sequence's length are never read.  Served where xgpr_conv_token_rows_ok(width, vocab, C) is 1 -- host code, no GPU: a
+ * window of up to 1024 elements (padded) and a table of at most 4608 floats, which the workgroup keeps in LDS beside its
+ * exchange buffers without losing a resident wave.  Elsewhere the entry points return XGPR_ERR_UNSUPPORTED and launch
+ * nothing: the caller expands slice by slice and calls the dense sibling.  vocab outside 1 .. 256 or C < 1:
+ * XGPR_ERR_ARRAY_DIMS; a NULL tokens / table / row pointer or a workspace smaller than the sign masks: XGPR_ERR_WORKSPACE. */
+int xgpr_conv_token_rows_ok(long width, long vocab, long C);
+int xgpr_conv_token_rows_f32(const uint8_t *tokens, const float *table, float *zc, const int8_t *radem, const float *chi,
+                             const int32_t *seqlen_host, const int32_t *seqlen_dev,
+                             long n, long L, long vocab, long C, long num_rffs, long num_freqs, long radem_shape2,
+                             long nseq, int conv_width, int scaling_type, int fit_intercept,
+                             void *workspace, size_t workspace_bytes, void *stream);
+int xgpr_conv_token_grad_rows_f32(const uint8_t *tokens, const float *table, float *zrows, float *grows, const int8_t *radem,
+                                  const float *chi, const int32_t *seqlen_host, const int32_t *seqlen_dev,
+                                  long n, long L, long vocab, long C, long num_rffs, long num_freqs, long radem_shape2,
+                                  long nseq, double sigma, int conv_width, int scaling_type, int fit_intercept,
+                                  void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- cudaConv1dMaxpool (xgpr_cuda_rfgen_cpp_ext.cpp:61-69): out[n, num_rffs] float32,
  * out = max(out, chi * sorf(window)) over k-mers; num_freqs == num_rffs;
  * radem_shape2 == reps * P exactly (conv1d_operations.cpp:65-68). */

@@ -32,6 +32,10 @@ SIGNATURES = {
     "xgpr_conv1d_fgen_f64": [_vp, _vp, _vp, _vp, _vp, _vp, _l, _l, _l, _l, _l, _l, _l, _l, _i, _i, _vp, _sz, _vp],
     "xgpr_conv_feature_rows_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _l, _l, _l, _l, _l, _l, _l, _i, _i, _i, _vp, _sz, _vp],
     "xgpr_conv_grad_rows_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _l, _l, _l, _l, _l, _l, _l, _d, _i, _i, _i, _vp, _sz, _vp],
+    "xgpr_conv_token_rows_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _l, _l, _l, _l, _l, _l, _l, _l, _i, _i, _i, _vp, _sz, _vp],
+    "xgpr_conv_token_grad_rows_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _l, _l, _l, _l, _l, _l, _l, _l, _d, _i, _i, _i,
+                                      _vp, _sz, _vp],
+    "xgpr_conv_token_rows_ok": [_l, _l, _l],
     "xgpr_conv_grad_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _l, _l, _l, _l, _l, _l, _l, _l, _l, _l, _d, _i, _i,
                            _vp, _sz, _vp],
     "xgpr_conv_grad_f64": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _l, _l, _l, _l, _l, _l, _l, _l, _l, _l, _d, _i, _i,

@@ -235,8 +235,7 @@ def predict_proba(kernel, weights, gamma, input_x, sequence_lengths=None, chunk_
         sl = None if sequence_lengths is None else sequence_lengths[i:i + chunk_size]
         fused = getattr(kernel, "supports_fused", False)
         if (fused or (seq_rows_ok(kernel) and sl is not None)) and kernel.block_ok() and weights.shape[1] <= 32:
-            from .kernels import scale_input
-            xs = scale_input(kernel._as_device_f32(input_x[i:i + chunk_size]), kernel.hyperparams[1])
+            xs = kernel.scaled_f32(input_x[i:i + chunk_size])
             zc = torch.empty((xs.shape[0], kernel.get_num_rffs()), dtype=torch.float32, device=kernel.device)
             if fused:
                 kernel.fill_feature_cache(xs, zc)

@@ -380,6 +380,27 @@ template <class F> int dispatch_conv_mode(int mode, F &&f) {
     }
 }
 
+// One launch of the sequence kernels on wave tiles (windows of up to 1024 elements), dense or token input: the sign masks, the
+// longest-first order when the caller's workspace has room for it (xgpr_conv_workspace_bytes) and there is more than one round of
+// waves to balance, then the kernel through `launch_kernel(args, nblocks)`.
+template <class F>
+int launch_wave_conv(WaveArgs a, const int8_t *radem, long R, long L, void *workspace, size_t wbytes, hipStream_t st, F &&launch_kernel) {
+    const long n = a.n;
+    int rc = pack_masks(radem, (uint64_t *)workspace, R, a.MW, st);
+    if (rc) return rc;
+    const long nblocks = (n * a.nb + 3) / 4;
+    if (nblocks > 2147483647L) return fail(XGPR_ERR_UNSUPPORTED, "too many datapoints for one launch");
+    const size_t order_off = masks_bytes(R);
+    if (n >= 64 && n <= 2147483647L && L <= 12000 && wbytes >= order_off + (size_t)n * sizeof(int32_t)) {
+        int32_t *order = reinterpret_cast<int32_t *>(reinterpret_cast<unsigned char *>(workspace) + order_off);
+        rc = launch(conv_order_kernel, dim3(1), dim3(1024), (size_t)(L + 1) * sizeof(int), st, "conv_order_kernel launch", a.seqlen,
+                    order, n, (int)L);
+        if (rc) return rc;
+        a.order = order;
+    }
+    return launch_kernel(a, nblocks);
+}
+
 template <typename T>
 int conv_impl(const T *x, double *out, double *grad, float *outf, const int8_t *radem, const T *chi,
               const int32_t *seqlen_host, const int32_t *seqlen_dev, long n, long L, long C, long out_rows,
@@ -422,24 +443,12 @@ int conv_impl(const T *x, double *out, double *grad, float *outf, const int8_t *
             a.conv_width = conv_width; a.scaling_type = scaling_type; a.fit_intercept = fit_intercept;
             a.scale = sqrt(1.0 / (double)num_freqs);
             if (grad_mode) { a.grad = grad; a.gradf = gradf; a.sigma = sigma; }
-            rc = pack_masks(radem, (uint64_t *)workspace, R, a.MW, st);
-            if (rc) return rc;
-            const long nblocks = (n * a.nb + 3) / 4;
-            if (nblocks > 2147483647L) return fail(XGPR_ERR_UNSUPPORTED, "too many datapoints for one launch");
-            // longest sequences first, when the caller's workspace has room for the order (xgpr_conv_workspace_bytes)
-            // and there is more than one round of waves to balance
-            const size_t order_off = masks_bytes(R);
-            if (n >= 64 && n <= 2147483647L && L <= 12000 && wbytes >= order_off + (size_t)n * sizeof(int32_t)) {
-                int32_t *order = reinterpret_cast<int32_t *>(reinterpret_cast<unsigned char *>(workspace) + order_off);
-                rc = launch(conv_order_kernel, dim3(1), dim3(1024), (size_t)(L + 1) * sizeof(int), st, "conv_order_kernel launch", seqlen_dev,
-                            order, n, (int)L);
-                if (rc) return rc;
-                a.order = order;
-            }
-            return dispatch_lg<1, 10>(lg, TOO_WIDE_WAVE, [&](auto LG) {
-                return dispatch_conv_mode(mode, [&](auto CM) {
-                    return launch(wave_conv_kernel<decltype(LG)::value, decltype(CM)::value>, dim3((unsigned)nblocks), dim3(256), 0, st,
-                                  "wave_conv_kernel launch", a);
+            return launch_wave_conv(a, radem, R, L, workspace, wbytes, st, [&](const WaveArgs &wa, long nblocks) {
+                return dispatch_lg<1, 10>(lg, TOO_WIDE_WAVE, [&](auto LG) {
+                    return dispatch_conv_mode(mode, [&](auto CM) {
+                        return launch(wave_conv_kernel<decltype(LG)::value, decltype(CM)::value>, dim3((unsigned)nblocks), dim3(256), 0, st,
+                                      "wave_conv_kernel launch", wa);
+                    });
                 });
             });
         }
@@ -529,6 +538,58 @@ int conv_rows_staged(const float *x, float *zrows, float *grows, const int8_t *r
         }
     }
     return 0;
+}
+
+// ---- token input for the float32 row writers (xgpr_conv_token_rows_f32 / xgpr_conv_token_grad_rows_f32): tokens[n, L] (uint8) index the
+// rows of table[vocab, C]; the rows are those of the dense siblings on the expanded array table[tokens], bit for bit.  Served by
+// wave_conv_tok_kernel where conv_token_rows_ok says so (a window of up to 1024 elements, a table that fits its LDS image); every other
+// shape is an error here and the caller expands (ConvSORFKernel does, slice by slice).
+int conv_token_rows_ok(long width, long vocab, long C) {
+    if (vocab < 1 || vocab > 256 || C < 1 || width < C || width % C != 0) return 0;
+    return padded_width(width) <= 1024 && vocab * C <= TOK_TABLE_FLOATS ? 1 : 0;
+}
+
+int conv_token_impl(const uint8_t *tokens, const float *table, float *zrows, float *grows, bool grad_mode, const int8_t *radem,
+                    const float *chi, const int32_t *seqlen_host, const int32_t *seqlen_dev, long n, long L, long vocab, long C,
+                    long num_rffs, long num_freqs, long R, long nseq, double sigma, int conv_width, int scaling_type, int fit_intercept,
+                    void *workspace, size_t wbytes, void *stream) {
+    if (vocab < 1 || vocab > 256) return fail(XGPR_ERR_ARRAY_DIMS, "token table: vocab must be 1 .. 256 (uint8 tokens)");
+    if (C < 1) return fail(XGPR_ERR_ARRAY_DIMS, "token table: needs at least one column");
+    const long win = (long)conv_width * C;
+    const long P = padded_width(win > 0 ? win : 1);
+    int rc = check_sorf_shape(n, num_rffs, num_freqs, R, P, 2, [&] {
+        if (nseq != n) return fail(XGPR_ERR_SEQLEN_SIZE, "wrong array sizes");
+        if (L < conv_width || conv_width <= 0) return fail(XGPR_ERR_CONV_WIDTH, "invalid conv_width");
+        return 0;
+    });
+    if (rc) return rc;
+    rc = check_seqlens(seqlen_host, nseq, n, L, conv_width);
+    if (rc) return rc;
+    if (!seqlen_dev) return fail(XGPR_ERR_WORKSPACE, "seqlen_dev (device copy of the sequence lengths) is required");
+    if (!tokens || !table) return fail(XGPR_ERR_WORKSPACE, "tokens and table are required");
+    if (!zrows || (reinterpret_cast<uintptr_t>(zrows) & 7) != 0) return fail(XGPR_ERR_WORKSPACE, "feature rows pointer must be 8-byte aligned");
+    if (grad_mode && (!grows || (reinterpret_cast<uintptr_t>(grows) & 7) != 0))
+        return fail(XGPR_ERR_WORKSPACE, "gradient rows pointer must be 8-byte aligned");
+    if (!conv_token_rows_ok(win, vocab, C))
+        return fail(XGPR_ERR_UNSUPPORTED, "token input serves windows of up to 1024 elements and tables of up to 4608 floats (see xgpr_conv_token_rows_ok)");
+    if (!workspace || wbytes < masks_bytes(R)) return fail(XGPR_ERR_WORKSPACE, "workspace too small (see xgpr_conv_feature_rows_workspace_bytes)");
+    hipStream_t st = (hipStream_t)stream;
+    WaveArgs a = wave_args(table, chi, workspace, n, L, win, num_freqs, R);
+    a.tokens = tokens; a.vocab = (int)vocab;
+    a.outf = zrows; a.seqlen = seqlen_dev; a.kmer_stride = (int)C;
+    a.conv_width = conv_width; a.scaling_type = scaling_type; a.fit_intercept = fit_intercept;
+    a.scale = sqrt(1.0 / (double)num_freqs);
+    if (grad_mode) { a.gradf = grows; a.sigma = sigma; }
+    const int lg = ilog2(P);
+    return launch_wave_conv(a, radem, R, L, workspace, wbytes, st, [&](const WaveArgs &wa, long nblocks) {
+        return dispatch_lg<1, 10>(lg, TOO_WIDE_WAVE, [&](auto LG) {
+            return dispatch_bool(grad_mode, [&](auto GR) {
+                constexpr int CM = decltype(GR)::value ? CONV_GRAD_ROWS : CONV_ROWS;
+                return launch(wave_conv_tok_kernel<decltype(LG)::value, CM>, dim3((unsigned)nblocks), dim3(256), 0, st,
+                              "wave_conv_tok_kernel launch", wa);
+            });
+        });
+    });
 }
 
 constexpr long ZTZ_MAX_SLABS = 2048;

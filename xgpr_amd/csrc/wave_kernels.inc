@@ -166,8 +166,68 @@ constexpr bool conv_is_grad(int mode) { return mode == CONV_GRAD || mode == CONV
 #define XGPR_CONV_C2_ALL 1          // the feature operator's tile takes the transposed-columns / rows-only path at EVERY window width <= 256
 #endif
 
-template <int LOG2P, int MODE>
-__global__ __launch_bounds__(256, (conv_is_grad(MODE) && LOG2P >= 7) ? 1 : (conv_is_feat(MODE) && (LOG2P >= 7 || XGPR_CONV_C2_ALL)) ? 3 : 2) void wave_conv_kernel(WaveArgs a) {
+// Where the k-mer windows come from is a policy of the kernel body (WIN): begin(a, i, lane) once per sequence, issue(j) starts the
+// fetch of window j into the policy's own registers, take(v) completes it into the tile (replicated over the tile's 1024 / P
+// transforms).  DenseWindows: the float32 array x[n, L, C], wave_load_base / wave_expand as before.
+template <int LOG2P> struct DenseWindows {
+    const float *xrow; int d, kmer_stride, lane;
+    float nx[TileBase<LOG2P>::N];
+    __device__ __forceinline__ void begin(const WaveArgs &a, long i, int lane_) {
+        xrow = a.x + i * a.row_stride; d = a.d; kmer_stride = a.kmer_stride; lane = lane_;
+    }
+    __device__ __forceinline__ void issue(int j) { wave_load_base<LOG2P>(nx, xrow + (long)j * kmer_stride, d, lane); }
+    __device__ __forceinline__ void take(float (&v)[16]) const { wave_expand<LOG2P>(v, nx); }
+};
+
+// TokenWindows: tokens[n, L] (uint8) index the rows of a table[V, C] that the workgroup holds in LDS (wave_conv_tok_kernel).  Element e
+// of window j is table[tokens[i, j + e / C]][e % C] for e < conv_width * C and 0.0f beyond.  (e / C, e % C) does not depend on j: begin()
+// works them out once per wave for the lane's N = P / 64 window registers -- the position as the byte offset of the token load, the
+// channel as a byte offset into the table image -- and the k-mer loop has no division.  Padding needs no select either: a padded
+// element's position is past the window's conv_width token bytes, the buffer range check answers token 0, and its channel offset points
+// at the one 0.0f kept behind the table (row 0 + that offset = the zero slot).  issue(j) puts the N token bytes of window j in flight
+// (global memory: a sequence's L bytes stay in L2, and one byte load per register replaces the dense float load one for one); take(v)
+// turns them into LDS addresses -- one multiply-add each -- and gathers.  Windows of 512 / 1024 elements keep position and channel
+// offset packed in ONE register per window register (16 fewer live registers at 1024; see conv_tok_min_blocks).
+// Token values are < V by the caller's contract (the dataset builders check it once).
+constexpr int TOK_TABLE_FLOATS = 4608;      // V * C at most: 18 KiB beside the 34 KiB of chi and exchange buffers, three workgroups per CU
+template <int LOG2P> struct TokenWindows {
+    static constexpr int N = TileBase<LOG2P>::N;
+    static constexpr bool PACK = N >= 8;
+    const uint8_t *trow; const char *tab; int cw; unsigned c4;
+    unsigned pos[N], cho[PACK ? 1 : N], tk[N];
+    __device__ __forceinline__ void begin(const WaveArgs &a, long i, int lane) {
+        constexpr int P = 1 << LOG2P;
+        trow = a.tokens + i * a.row_stride; cw = a.conv_width; c4 = 4u * (unsigned)a.kmer_stride;
+        const unsigned C = (unsigned)a.kmer_stride, zero4 = 4u * (unsigned)a.vocab * C;
+        #pragma unroll
+        for (int r = 0; r < N; r++) {
+            const unsigned e = P >= 64 ? (unsigned)(r * 64 + lane) : (unsigned)(lane & (P - 1));
+            const unsigned q = e / C;
+            const bool ok = e < (unsigned)a.d;
+            const unsigned p = ok ? q : 0xffffu, c = ok ? 4u * (e - q * C) : zero4;      // (conv_width <= 1024 < 0xffff: out of range)
+            if constexpr (PACK) pos[r] = p | (c << 16);
+            else { pos[r] = p; cho[r] = c; }
+        }
+    }
+    __device__ __forceinline__ void issue(int j) {
+        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(trow + j), 0, cw, 0x00020000);
+        #pragma unroll
+        for (int r = 0; r < N; r++) tk[r] = __builtin_amdgcn_raw_buffer_load_b8(rs, (int)(PACK ? pos[r] & 0xffffu : pos[r]), 0, 0);
+    }
+    __device__ __forceinline__ void take(float (&v)[16]) const {
+        float nx[N];
+        #pragma unroll
+        for (int r = 0; r < N; r++) nx[r] = *reinterpret_cast<const float *>(tab + (tk[r] * c4 + (PACK ? pos[r] >> 16 : cho[r])));
+        wave_expand<LOG2P>(v, nx);
+    }
+};
+
+constexpr int conv_min_blocks(int LOG2P, int MODE) {
+    return (conv_is_grad(MODE) && LOG2P >= 7) ? 1 : (conv_is_feat(MODE) && (LOG2P >= 7 || XGPR_CONV_C2_ALL)) ? 3 : 2;
+}
+
+template <int LOG2P, int MODE, class WIN>
+__device__ __forceinline__ void wave_conv_body(const WaveArgs &a, WIN &win) {
     constexpr bool MAXPOOL = MODE == CONV_MAXPOOL;
     const int lane = threadIdx.x & 63;
     const long item = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) + (long)blockIdx.x * 4;
@@ -223,11 +283,10 @@ __global__ __launch_bounds__(256, (conv_is_grad(MODE) && LOG2P >= 7) ? 1 : (conv
             __builtin_amdgcn_s_setprio(0);
         } else tile_sorf<LOG2P, TP, TP>(t, mk, sw, tb, a.MW, a.nc, lane);
     };
-    const float *xrow = a.x + i * a.row_stride;
     // the window of k-mer j + 1 is fetched while k-mer j is transformed (the loads used to sit at the top of
     // every iteration, exposing a global-memory round trip per k-mer)
-    float nx[TileBase<LOG2P>::N];
-    wave_load_base<LOG2P>(nx, xrow, a.d, lane);
+    win.begin(a, i, lane);
+    win.issue(0);
     if constexpr (MAXPOOL) {
         float acc[16];
         float *orow = a.outf + i * a.F;
@@ -239,8 +298,8 @@ __global__ __launch_bounds__(256, (conv_is_grad(MODE) && LOG2P >= 7) ? 1 : (conv
         for (int j = 0; j < nk; j++) {
             mk = launder(mk);
             float v[16];
-            wave_expand<LOG2P>(v, nx);
-            wave_load_base<LOG2P>(nx, xrow + (long)(j + 1 < nk ? j + 1 : j) * a.kmer_stride, a.d, lane);   // next window
+            win.take(v);
+            win.issue(j + 1 < nk ? j + 1 : j);                                                              // next window
             sorf_tile(v);
             #pragma unroll
             for (int r = 0; r < 16; r++) {
@@ -265,8 +324,8 @@ __global__ __launch_bounds__(256, (conv_is_grad(MODE) && LOG2P >= 7) ? 1 : (conv
         for (int j = 0; j < nk; j++) {
             mk = launder(mk);
             float v[16], gv[16], sn[16], cs[16];
-            wave_expand<LOG2P>(v, nx);
-            wave_load_base<LOG2P>(nx, xrow + (long)(j + 1 < nk ? j + 1 : j) * a.kmer_stride, a.d, lane);   // next window
+            win.take(v);
+            win.issue(j + 1 < nk ? j + 1 : j);                                                              // next window
             sorf_tile(v);
             #pragma unroll
             for (int r = 0; r < 16; r++) { gv[r] = v[r] * ch[r]; v[r] = (float)(gv[r] * a.sigma); }
@@ -318,9 +377,8 @@ __global__ __launch_bounds__(256, (conv_is_grad(MODE) && LOG2P >= 7) ? 1 : (conv
             mk = launder(mk);
             if constexpr (TP || C2) asm volatile("" : "+v"(sw[0]), "+v"(sw[1]), "+v"(sw[2]));   // three registers, not 48 hoisted masks
             float v[16], sn[16], cs[16];
-            wave_expand<LOG2P>(v, nx);
-            const float *xnext = xrow + (long)(j + 1 < nk ? j + 1 : j) * a.kmer_stride;                     // next window
-            wave_load_base<LOG2P>(nx, xnext, a.d, lane);
+            win.take(v);
+            win.issue(j + 1 < nk ? j + 1 : j);                                                              // next window
             sorf_tile(v);
             if constexpr (CHI_LDS) {
                 wave_lds_sync();
@@ -378,6 +436,34 @@ __global__ __launch_bounds__(256, (conv_is_grad(MODE) && LOG2P >= 7) ? 1 : (conv
             }
         }
     }
+}
+
+template <int LOG2P, int MODE>
+__global__ __launch_bounds__(256, conv_min_blocks(LOG2P, MODE)) void wave_conv_kernel(WaveArgs a) {
+    DenseWindows<LOG2P> win;
+    wave_conv_body<LOG2P, MODE>(a, win);
+}
+
+// the token forms (xgpr_conv_token_rows_f32 / xgpr_conv_token_grad_rows_f32: MODE CONV_ROWS / CONV_GRAD_ROWS).  a.x is the table [vocab,
+// kmer_stride] -- sigma-scaled for the feature rows, unscaled for the gradient rows, as x is --, a.tokens the uint8 [n, row_stride]
+// array, a.d = conv_width * kmer_stride.  The workgroup copies the table into LDS once, with one 0.0f behind it, before any wave leaves.
+// Windows of 512 / 1024 elements: the dense feature rows sit exactly at the 168 registers of three waves per SIMD, and the token form
+// holds 8 / 16 index registers more through the loop -- bound to three waves it spills 6 / 30 registers to scratch; it is built for two.
+constexpr int conv_tok_min_blocks(int LOG2P, int MODE) {
+    return (MODE == CONV_ROWS && LOG2P >= 9) ? 2 : conv_min_blocks(LOG2P, MODE);
+}
+
+template <int LOG2P, int MODE>
+__global__ __launch_bounds__(256, conv_tok_min_blocks(LOG2P, MODE)) void wave_conv_tok_kernel(WaveArgs a) {
+    static_assert(MODE == CONV_ROWS || MODE == CONV_GRAD_ROWS, "token input serves the float32 row writers");
+    __shared__ __attribute__((aligned(16))) float tab[TOK_TABLE_FLOATS + 4];
+    const int nt = a.vocab * a.kmer_stride;             // <= TOK_TABLE_FLOATS (conv_token_rows_ok)
+    for (int t = threadIdx.x; t < nt; t += 256) tab[t] = a.x[t];
+    if (threadIdx.x == 0) tab[nt] = 0.0f;
+    __syncthreads();
+    TokenWindows<LOG2P> win;
+    win.tab = reinterpret_cast<const char *>(tab);
+    wave_conv_body<LOG2P, MODE>(a, win);
 }
 
 // sum of a double over the 64 lanes, returned wave-uniform.  Rows of 16 lanes are reduced with

@@ -759,5 +759,6 @@ struct WaveArgs {
     const int32_t *order;         // convolution operators: processing order of the sequences (or null)
     int dma1;                     // three-wave kernel: rows are not whole aligned 16-byte groups -- fetch them float by float
     float *gradf;                 // OUT_GRAD_ROWS: the float32 gradient rows (the feature rows go to outf)
+    const uint8_t *tokens; int vocab;   // token forms of the sequence kernels: tokens [n, row_stride]; x is then the table [vocab, kmer_stride]
 };
 

@@ -198,6 +198,22 @@ int xgpr_conv_grad_rows_f32(const float *x, float *zrows, float *grows, const in
                             radem_shape2, nseq, sigma, conv_width, scaling_type, MODE_CONV_GRAD_ROWS, workspace, workspace_bytes,
                             stream, fit_intercept != 0, grows);
 }
+int xgpr_conv_token_rows_ok(long width, long vocab, long C) { return conv_token_rows_ok(width, vocab, C); }
+int xgpr_conv_token_rows_f32(const uint8_t *tokens, const float *table, float *zc, const int8_t *radem, const float *chi,
+                             const int32_t *seqlen_host, const int32_t *seqlen_dev, long n, long L, long vocab, long C,
+                             long num_rffs, long num_freqs, long radem_shape2, long nseq, int conv_width, int scaling_type,
+                             int fit_intercept, void *workspace, size_t workspace_bytes, void *stream) {
+    return conv_token_impl(tokens, table, zc, nullptr, false, radem, chi, seqlen_host, seqlen_dev, n, L, vocab, C, num_rffs, num_freqs,
+                           radem_shape2, nseq, 0.0, conv_width, scaling_type, fit_intercept != 0, workspace, workspace_bytes, stream);
+}
+int xgpr_conv_token_grad_rows_f32(const uint8_t *tokens, const float *table, float *zrows, float *grows, const int8_t *radem,
+                                  const float *chi, const int32_t *seqlen_host, const int32_t *seqlen_dev, long n, long L,
+                                  long vocab, long C, long num_rffs, long num_freqs, long radem_shape2, long nseq, double sigma,
+                                  int conv_width, int scaling_type, int fit_intercept, void *workspace, size_t workspace_bytes,
+                                  void *stream) {
+    return conv_token_impl(tokens, table, zrows, grows, true, radem, chi, seqlen_host, seqlen_dev, n, L, vocab, C, num_rffs, num_freqs,
+                           radem_shape2, nseq, sigma, conv_width, scaling_type, fit_intercept != 0, workspace, workspace_bytes, stream);
+}
 int xgpr_conv_grad_f64(const double *x, double *out, double *grad, const int8_t *radem, const double *chi,
                        const int32_t *seqlen_host, const int32_t *seqlen_dev, long n, long L, long C, long out_rows,
                        long num_rffs, long grad_rows, long grad_cols, long num_freqs, long radem_shape2, long nseq,

@@ -14,6 +14,83 @@ import torch
 from .dist import SINGLE
 
 
+class TokenBatch:
+    """Sequences given as tokens: ``tokens`` (uint8 [n, L]) index the rows of ``table`` (float32 [V, C], V <= 256: a one-hot
+    or substitution-matrix encoding), standing for the dense float32 array ``table[tokens]`` of shape [n, L, C] at 1 byte
+    per position instead of 4 C.  It has what the solver passes need of the shard -- ``shape``, row slicing and row
+    selection, which return a TokenBatch over the same table -- and is what the token feature-row operators read
+    (``ConvSORFKernel.fill_feature_rows`` / ``fill_grad_rows``).  Token values are < V: the dataset builders check it once."""
+
+    def __init__(self, tokens, table):
+        if tokens.dim() != 2 or tokens.dtype != torch.uint8:
+            raise RuntimeError("tokens must be a 2d uint8 array [N, L].")
+        if table.dim() != 2 or table.dtype != torch.float32 or not 1 <= table.shape[0] <= 256:
+            raise RuntimeError("token_table must be a 2d float32 array [V, C] with 1 <= V <= 256.")
+        self.tokens, self.table = tokens, table
+
+    @property
+    def shape(self):
+        return (self.tokens.shape[0], self.tokens.shape[1], self.table.shape[1])
+
+    @property
+    def device(self):
+        return self.tokens.device
+
+    @property
+    def is_cuda(self):
+        return self.tokens.is_cuda
+
+    def dim(self):
+        return 3
+
+    def __len__(self):
+        return self.tokens.shape[0]
+
+    def __getitem__(self, rows):
+        """``tb[lo:hi]``, ``tb[idx]`` (an index tensor / array / list): rows only, the same table."""
+        if isinstance(rows, tuple):
+            if any(r is not Ellipsis for r in rows[1:]):
+                raise IndexError("a TokenBatch is indexed by rows only.")
+            rows = rows[0]
+        if isinstance(rows, int):
+            raise IndexError("a TokenBatch is indexed by a slice or an index array, not a single row.")
+        if isinstance(rows, (np.ndarray, list)):
+            rows = torch.as_tensor(rows, device=self.tokens.device)
+        return TokenBatch(self.tokens[rows], self.table)
+
+    def to(self, device):
+        return TokenBatch(self.tokens.to(device), self.table.to(device))
+
+    def scaled(self, sigma):
+        """The same tokens over ``scale_input(table, sigma)``: elementwise what ``scale_input`` makes of the dense array."""
+        from .kernels import scale_input
+        return TokenBatch(self.tokens, scale_input(self.table, sigma))
+
+    def dense(self):
+        """The float32 [n, L, C] array this batch stands for."""
+        return self.table[self.tokens.long()]
+
+
+def _dense_chunk(x):
+    return x.dense() if isinstance(x, TokenBatch) else x
+
+
+def token_batch(xdata, token_table):
+    """The checks of token input, made once: integer tokens [N, L] in [0, V) over a 2d float table -> TokenBatch."""
+    tab = torch.from_numpy(np.ascontiguousarray(token_table)) if isinstance(token_table, np.ndarray) else token_table
+    if not isinstance(tab, torch.Tensor) or tab.dim() != 2 or not tab.is_floating_point():
+        raise RuntimeError("token_table must be a 2d floating-point array [V, C].")
+    if not 1 <= tab.shape[0] <= 256 or tab.shape[1] < 1:
+        raise RuntimeError("token_table must have 1 to 256 rows (uint8 tokens) and at least one column.")
+    if isinstance(xdata, TokenBatch):
+        raise RuntimeError("With token_table, xdata is the integer token array itself.")
+    if xdata.dim() != 2 or xdata.is_floating_point() or xdata.is_complex() or xdata.dtype == torch.bool:
+        raise RuntimeError("With token_table, xdata must be a 2d array of integer tokens [N, L].")
+    if xdata.numel() > 0 and (int(xdata.min()) < 0 or int(xdata.max()) >= tab.shape[0]):
+        raise RuntimeError(f"Tokens must lie in [0, {tab.shape[0]}), the rows of token_table.")
+    return TokenBatch(xdata.to(torch.uint8), tab.to(torch.float32))
+
+
 class DeviceDataset:
     def __init__(self, xdata, ydata, sequence_lengths=None, chunk_size=2000,
                  trainy_mean=0.0, trainy_std=1.0, ndatapoints=None, device="cuda", comm=SINGLE, max_class=None):
@@ -70,17 +147,17 @@ class DeviceDataset:
             else:                                  # class labels go through unchanged
                 ychunk = self._ydata[i:j]
             lchunk = None if self._sequence_lengths is None else self._sequence_lengths[i:j]
-            yield self._xdata[i:j, ...], ychunk, lchunk
+            yield _dense_chunk(self._xdata[i:j, ...]), ychunk, lchunk
 
     def get_chunked_x_data(self):
         n = self._xdata.shape[0]
         for i in range(0, n, self._chunk_size):
             j = min(i + self._chunk_size, n)
             lchunk = None if self._sequence_lengths is None else self._sequence_lengths[i:j]
-            yield self._xdata[i:j, ...], lchunk
+            yield _dense_chunk(self._xdata[i:j, ...]), lchunk
 
     def get_xdata(self):
-        """The whole resident shard of x (device tensor)."""
+        """The whole resident shard of x (device tensor; a TokenBatch for a token dataset)."""
         return self._xdata
 
     def get_sequence_lengths(self):
@@ -126,6 +203,8 @@ class DeviceDataset:
         copy, sorf_kernel_baseclass.py:117), cached per sigma for the fused kernels."""
         from .kernels import scale_input, padded_dims
         key = float(sigma)
+        if isinstance(self._xdata, TokenBatch):      # the table is what is scaled: no dense array, nothing worth caching
+            return self._xdata.scaled(key)
         if key not in self._scaled:
             xs = scale_input(self._xdata, key)
             # rows a multiple of four floats (zero columns appended, which is what the transform's own zero padding up
@@ -139,13 +218,25 @@ class DeviceDataset:
         return self._scaled[key]
 
 
+def _resident_x(xt, device):
+    if isinstance(xt, TokenBatch):
+        return TokenBatch(xt.tokens.to(device).contiguous(), xt.table.to(device).contiguous())
+    return xt.to(device=device, dtype=torch.float32).contiguous()
+
+
 def build_regression_dataset(xdata, ydata, sequence_lengths=None, chunk_size=2000, device="cuda",
-                             comm=SINGLE, already_sharded=False):
+                             comm=SINGLE, already_sharded=False, token_table=None):
     """dataset_builder.py:14-178 for in-memory arrays.  ``xdata`` / ``ydata`` are numpy arrays
     or tensors; with ``comm.world_size > 1`` each rank keeps rows ``comm.shard_bounds(N)`` unless
-    ``already_sharded`` (then the arrays passed are this rank's rows)."""
+    ``already_sharded`` (then the arrays passed are this rank's rows).  ``token_table`` (float [V, C], V <= 256):
+    ``xdata`` is an integer array [N, L] of tokens in [0, V) standing for the sequences ``token_table[xdata]``; the
+    dataset keeps tokens and table only (a TokenBatch), ``sequence_lengths`` is required."""
     xt = torch.from_numpy(np.ascontiguousarray(xdata)) if isinstance(xdata, np.ndarray) else xdata
     yt = torch.from_numpy(np.ascontiguousarray(ydata)) if isinstance(ydata, np.ndarray) else ydata
+    if token_table is not None:
+        if sequence_lengths is None:
+            raise RuntimeError("sequence_lengths is required with token_table.")
+        xt = token_batch(xt, token_table)
     if xt.shape[0] != yt.shape[0]:
         raise RuntimeError("Different number of datapoints in x and y.")
     sl = sequence_lengths
@@ -160,7 +251,7 @@ def build_regression_dataset(xdata, ydata, sequence_lengths=None, chunk_size=200
         xt, yt = xt[lo:hi], yt[lo:hi]
         if sl is not None:
             sl = sl[lo:hi]
-    xt = xt.to(device=device, dtype=torch.float32).contiguous()
+    xt = _resident_x(xt, device)
     yt = yt.to(device=device, dtype=torch.float64).contiguous()
     # global mean / population std (numpy's .std()), two passes in float64
     stats = torch.stack([yt.sum(), torch.tensor(float(yt.shape[0]), dtype=torch.float64, device=device)])
@@ -174,12 +265,16 @@ def build_regression_dataset(xdata, ydata, sequence_lengths=None, chunk_size=200
 
 
 def build_classification_dataset(xdata, ydata, sequence_lengths=None, chunk_size=2000, device="cuda",
-                                 comm=SINGLE, already_sharded=False):
+                                 comm=SINGLE, already_sharded=False, token_table=None):
     """dataset_builder.py:68-117, :150-190 for in-memory arrays: integer labels in [0, max_class] with a
-    zero category, no y normalisation.  Sharding as in ``build_regression_dataset``; the class count is
-    global."""
+    zero category, no y normalisation.  Sharding and ``token_table`` as in ``build_regression_dataset``; the class
+    count is global."""
     xt = torch.from_numpy(np.ascontiguousarray(xdata)) if isinstance(xdata, np.ndarray) else xdata
     yt = torch.from_numpy(np.ascontiguousarray(ydata)) if isinstance(ydata, np.ndarray) else ydata
+    if token_table is not None:
+        if sequence_lengths is None:
+            raise RuntimeError("sequence_lengths is required with token_table.")
+        xt = token_batch(xt, token_table)
     if yt.dim() != 1:
         raise RuntimeError("Y must be a 1d numpy array.")
     if yt.is_floating_point() or yt.dtype == torch.bool:
@@ -198,7 +293,7 @@ def build_classification_dataset(xdata, ydata, sequence_lengths=None, chunk_size
         xt, yt = xt[lo:hi], yt[lo:hi]
         if sl is not None:
             sl = sl[lo:hi]
-    xt = xt.to(device=device, dtype=torch.float32).contiguous()
+    xt = _resident_x(xt, device)
     yt = yt.to(device=device, dtype=torch.int64).contiguous()
     # [max label, -min label, local row count]: max-reduce the first two, sum the third
     ext = torch.stack([yt.max(), -yt.min()]).to(torch.float64)

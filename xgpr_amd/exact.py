@@ -139,12 +139,11 @@ def predict_mean(kernel, weights, input_x, trainy_mean, trainy_std, sequence_len
     # the sequence kernels likewise: a chunk's complete float32 rows (intercept column included: no flag, scale 1)
     seq = not fused and seq_rows_ok(kernel) and kernel.block_ok() and sequence_lengths is not None
     if fused or seq:
-        from .kernels import scale_input
         wcol = weights.to(torch.float64).reshape(-1, 1).contiguous()
     for i in range(0, input_x.shape[0], chunk_size):
         sl = None if sequence_lengths is None else sequence_lengths[i:i + chunk_size]
         if fused or seq:
-            xs = scale_input(kernel._as_device_f32(input_x[i:i + chunk_size]), kernel.hyperparams[1])
+            xs = kernel.scaled_f32(input_x[i:i + chunk_size])
             zc = torch.empty((xs.shape[0], kernel.get_num_rffs()), dtype=torch.float32, device=kernel.device)
             pred = torch.empty((xs.shape[0], 1), dtype=torch.float64, device=kernel.device)
             if fused:

@@ -19,6 +19,7 @@ import torch
 from scipy.stats import chi as _chi
 
 from . import xgpr_hip_rfgen_ext as ext
+from .dataset import TokenBatch
 
 
 def padded_dims(width):
@@ -73,12 +74,21 @@ class KernelBase:
     def _as_device(self, input_x):
         if isinstance(input_x, np.ndarray):
             input_x = torch.from_numpy(np.ascontiguousarray(input_x))
+        if isinstance(input_x, TokenBatch):          # the float64 operators take the dense array: a chunk of it is small and transient
+            return input_x.to(self.device).dense()
         return input_x.to(self.device)
 
     def _as_device_f32(self, input_x):
         """the private float32 copy every transform starts from (kernel_baseclass.py:274-288): float64 inputs
         are rounded to float32 BEFORE sigma is applied, as the reference does"""
         return self._as_device(input_x).to(torch.float32)
+
+    def scaled_f32(self, input_x):
+        """The private float32 copy of a chunk multiplied by sigma, on the device (what every transform starts from); a
+        TokenBatch keeps its tokens and has its table scaled -- elementwise the same values."""
+        if isinstance(input_x, TokenBatch):
+            return input_x.to(self.device).scaled(self.hyperparams[1])
+        return scale_input(self._as_device_f32(input_x), self.hyperparams[1])
 
     def transform_x(self, input_x, sequence_length=None):
         """kernel_baseclass.py:269-299: private float32 copy -> kernel_specific_transform ->
@@ -364,11 +374,34 @@ class ConvSORFKernel(KernelBase):
             sequence_length = sequence_length.cpu().numpy()
         return np.ascontiguousarray(sequence_length.astype(np.int32, copy=False))
 
+    def token_rows_ok(self, batch):
+        """Whether the token operators serve ``batch`` for this kernel (ext.conv_token_rows_ok: a window of up to 1024
+        elements, a table that fits the kernels' LDS image); otherwise its rows come from dense slices."""
+        return (self.seq_rows_ok() and batch.is_cuda and batch.tokens.is_contiguous()
+                and ext.conv_token_rows_ok(self.conv_width * batch.shape[2], batch.table.shape[0], batch.shape[2]) == 1)
+
+    def _dense_slices(self, batch, lengths):
+        """(lo, hi, dense float32 slice, its lengths) over a TokenBatch the token operators do not serve: at most
+        ``CACHE_BUILD_ROWS`` sequences are expanded at a time."""
+        for lo in range(0, batch.shape[0], self.CACHE_BUILD_ROWS):
+            hi = min(lo + self.CACHE_BUILD_ROWS, batch.shape[0])
+            yield lo, hi, batch[lo:hi].dense().contiguous(), lengths[lo:hi]
+
     def fill_feature_rows(self, x_scaled, sequence_length, rows_out):
         """rows_out [n, num_rffs] float32 <- ``transform_x`` of the (already sigma-scaled, float32) sequences, rounded
-        to float32: overwritten, bit-identical to ``transform_x(...).to(torch.float32)``."""
-        ext.hipConvFeatureRows(x_scaled, rows_out, self.radem_diag, self.chi_arr,
-                               self._host_lengths(x_scaled, sequence_length), self.conv_width, self.scaling_type,
+        to float32: overwritten, bit-identical to ``transform_x(...).to(torch.float32)``.  ``x_scaled`` may be a
+        TokenBatch over the sigma-scaled table: the token operator reads it as it is (same bits as the dense array)."""
+        lengths = self._host_lengths(x_scaled, sequence_length)
+        if isinstance(x_scaled, TokenBatch):
+            if self.token_rows_ok(x_scaled):
+                ext.hipConvTokenRows(x_scaled.tokens, x_scaled.table, rows_out, self.radem_diag, self.chi_arr, lengths,
+                                     self.conv_width, self.scaling_type, self.fit_intercept)
+                return
+            for lo, hi, xd, lens in self._dense_slices(x_scaled, lengths):
+                ext.hipConvFeatureRows(xd, rows_out[lo:hi], self.radem_diag, self.chi_arr, lens, self.conv_width,
+                                       self.scaling_type, self.fit_intercept)
+            return
+        ext.hipConvFeatureRows(x_scaled, rows_out, self.radem_diag, self.chi_arr, lengths, self.conv_width, self.scaling_type,
                                self.fit_intercept)
 
     def grad_rows_ok(self):
@@ -381,8 +414,17 @@ class ConvSORFKernel(KernelBase):
         """zrows, grows [w, M] float32 <- the complete feature rows and d(features)/d(sigma) rows of the UNSCALED float32
         sequences: ``gradient_x`` rounded once to float32 (its entries are float64 sums over k-mers of float32 values),
         intercept column included.  Both overwritten."""
-        ext.hipConvGradRows(x_unscaled, zrows, grows, self.radem_diag, self.chi_arr,
-                            self._host_lengths(x_unscaled, sequence_length), float(self.hyperparams[1]), self.conv_width,
+        lengths, sigma = self._host_lengths(x_unscaled, sequence_length), float(self.hyperparams[1])
+        if isinstance(x_unscaled, TokenBatch):       # (the UNSCALED table, as x is)
+            if self.token_rows_ok(x_unscaled):
+                ext.hipConvTokenGradRows(x_unscaled.tokens, x_unscaled.table, zrows, grows, self.radem_diag, self.chi_arr,
+                                         lengths, sigma, self.conv_width, self.scaling_type, self.fit_intercept)
+                return
+            for lo, hi, xd, lens in self._dense_slices(x_unscaled, lengths):
+                ext.hipConvGradRows(xd, zrows[lo:hi], grows[lo:hi], self.radem_diag, self.chi_arr, lens, sigma,
+                                    self.conv_width, self.scaling_type, self.fit_intercept)
+            return
+        ext.hipConvGradRows(x_unscaled, zrows, grows, self.radem_diag, self.chi_arr, lengths, sigma, self.conv_width,
                             self.scaling_type, self.fit_intercept)
 
     def transform_x(self, input_x, sequence_length=None, rows_out=None, pre_scaled=False):
@@ -392,7 +434,7 @@ class ConvSORFKernel(KernelBase):
         (``dataset.scaled_x``), so it is not scaled again."""
         if rows_out is None:
             return super().transform_x(input_x, sequence_length)
-        xin = input_x if pre_scaled else scale_input(self._as_device_f32(input_x), self.hyperparams[1])
+        xin = input_x if pre_scaled else self.scaled_f32(input_x)
         self.fill_feature_rows(xin, sequence_length, rows_out)
         return rows_out
 
@@ -617,6 +659,8 @@ class Conv1dTwoLayerKernel(KernelBase):
     def fill_grad_rows(self, x_unscaled, zrows, grows, sequence_length):
         """zrows, grows [w, M] float32 <- ``gradient_x`` of the UNSCALED float32 sequences, exactly: the gradient is
         hipRBFGrad over the max-pooled float32 first-layer features, every entry of which is a float32 value."""
+        if isinstance(x_unscaled, TokenBatch):
+            x_unscaled = x_unscaled.dense()
         ext.hipRBFGradRows(self._first_layer(x_unscaled, sequence_length), zrows, grows, self.radem_diag, self.chi_arr,
                            float(self.hyperparams[1]), self.fit_intercept)
 

@@ -17,6 +17,7 @@ from . import nmll as _nmll
 from .cg import cg_fit_lib_internal
 from .classification import fit_classifier, predict_proba
 from .exact import calc_weights_exact, calc_variance_exact
+from .dataset import TokenBatch, token_batch
 from .kernels import make_kernel
 from .preconditioner import RandNysPreconditioner, autoselect_preconditioner
 from .crude_tuning import tune_hyperparams_crude as _tune_crude
@@ -25,6 +26,15 @@ from .tuning import tune_hyperparams as _tune
 MAX_VARIANCE_RFFS = 4096            # constants.py:2
 MAX_CLOSED_FORM_RFFS = 8192         # constants.py:3
 DEFAULT_KERNEL_SPEC_PARMS = {"matern_nu": 5 / 2, "intercept": True, "averaging": "none"}      # constants.py:7-8
+
+
+def token_input(input_x, token_table, device):
+    """``predict`` input: a TokenBatch as it is; with ``token_table`` an integer array [N, L] of tokens in [0, V) over that
+    table, as a TokenBatch on ``device`` (the checks of the dataset builders); anything else unchanged."""
+    if token_table is None:
+        return input_x
+    xt = torch.from_numpy(np.ascontiguousarray(input_x)) if isinstance(input_x, np.ndarray) else input_x
+    return token_batch(xt, token_table).to(device)
 
 
 class _ModelBase:
@@ -80,7 +90,7 @@ class _ModelBase:
         return pre, pre.achieved_ratio
 
     def _to_device(self, arr):
-        return arr if isinstance(arr, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(arr))
+        return arr if isinstance(arr, (torch.Tensor, TokenBatch)) else torch.from_numpy(np.ascontiguousarray(arr))
 
 
 class xGPRegression(_ModelBase):
@@ -110,8 +120,11 @@ class xGPRegression(_ModelBase):
         if run_diagnostics:
             return n_iter, losses
 
-    def predict(self, input_x, sequence_lengths=None, get_var=False, chunk_size=2000):
-        """xgp_regression.py:77-148 -> numpy predictions (and variances)."""
+    def predict(self, input_x, sequence_lengths=None, get_var=False, chunk_size=2000, token_table=None):
+        """xgp_regression.py:77-148 -> numpy predictions (and variances).  ``input_x`` may be a TokenBatch, or with
+        ``token_table`` an integer token array [N, L]: the mean goes through the token feature rows, the variance through
+        dense chunks."""
+        input_x = token_input(input_x, token_table, self.device)
         if self.weights is None:
             raise RuntimeError("Model has not yet been successfully fitted.")
         if get_var and self.var is None:
@@ -185,10 +198,11 @@ class xGPClassification(_ModelBase):
         if run_diagnostics:
             return n_iter, losses
 
-    def predict(self, input_x, sequence_lengths=None, chunk_size=2000):
-        """xgp_classification.py:59-109 -> numpy [N, classes] probabilities."""
+    def predict(self, input_x, sequence_lengths=None, chunk_size=2000, token_table=None):
+        """xgp_classification.py:59-109 -> numpy [N, classes] probabilities.  Token input as ``xGPRegression.predict``."""
         if self.gamma is None:
             raise RuntimeError("Model has not been fitted yet.")
+        input_x = token_input(input_x, token_table, self.device)
         return predict_proba(self.kernel, self.weights, self.gamma, self._to_device(input_x), sequence_lengths,
                              chunk_size).cpu().numpy()
 
@@ -210,8 +224,9 @@ class KernelFGen:
             full[1:] = hyperparams
         self.kernel.set_hyperparams(full, logspace=True)
 
-    def predict(self, input_x, sequence_lengths=None, chunk_size=2000):
-        """-> numpy [N, num_rffs]"""
+    def predict(self, input_x, sequence_lengths=None, chunk_size=2000, token_table=None):
+        """-> numpy [N, num_rffs].  Token input (a TokenBatch, or integer tokens with ``token_table``) is expanded chunk by chunk."""
+        input_x = token_input(input_x, token_table, self.device)
         preds = []
         for i in range(0, input_x.shape[0], chunk_size):
             sl = None if sequence_lengths is None else sequence_lengths[i:i + chunk_size]

@@ -143,6 +143,9 @@ def _grad_rows_route(dataset, kernel):
     if fn is None or not hasattr(dataset, "get_xdata") or not fn():
         return False
     xall = dataset.get_xdata()
+    from .dataset import TokenBatch
+    if isinstance(xall, TokenBatch):      # tokens over a table: the sequence writers read them as they are (or expand slices)
+        return xall.is_cuda and _seq_grad_kernel(kernel) and dataset.get_sequence_lengths() is not None
     if not (isinstance(xall, torch.Tensor) and xall.is_cuda and xall.dtype == torch.float32 and xall.is_contiguous()):
         return False
     if xall.dim() == 3:

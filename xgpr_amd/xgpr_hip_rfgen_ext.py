@@ -471,6 +471,65 @@ def hipConvGradRows(inputArr, zRows, gRows, radem, chiArr, seqlengths, sigma, co
         _stream()))
 
 
+def conv_token_rows_ok(width, vocab, C):
+    """1 where hipConvTokenRows / hipConvTokenGradRows serve a window of ``width`` = conv_width * C elements over a table of
+    ``vocab`` rows and ``C`` columns, 0 otherwise (xgpr_conv_token_rows_ok; no device work)."""
+    return int(_LIB.xgpr_conv_token_rows_ok(int(width), int(vocab), int(C)))
+
+
+def _float_rows(t, nm, n):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or t.dim() != 2:
+        raise TypeError(f"{nm}: expected a 2-d float32 device tensor")
+    if t.shape[0] != n:
+        raise RuntimeError("no datapoints")
+    if t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) != t.shape[1]):
+        raise TypeError(f"{nm}: expected rows of M contiguous floats, M floats apart")
+    return C.c_void_p(t.data_ptr())
+
+
+@_array_args("tokens", "table", "rows_out", "radem", "chi")
+def hipConvTokenRows(tokens, table, rows_out, radem, chi, seqlen, conv_width, scaling_type, fit_intercept):
+    """hipConvFeatureRows for sequences given as tokens (xgpr_conv_token_rows_f32): ``tokens`` [N, L] uint8 index the rows
+    of ``table`` [V, C] float32 (already sigma-scaled), and ``rows_out`` [N, num_rffs] float32 is OVERWRITTEN with exactly the
+    rows hipConvFeatureRows writes for the dense array ``table[tokens]``.  Shapes for which ``conv_token_rows_ok`` is 0 raise
+    RuntimeError and launch nothing."""
+    t = _dev(tokens, "tokens", torch.uint8, 2)
+    tab = _dev(table, "table", torch.float32, 2)
+    n = tokens.shape[0]
+    zc = _float_rows(rows_out, "rows_out", n)
+    r = _radem3(radem)
+    c = _dev(chi, "chi", torch.float32, 1)
+    host, dev = _seqlens(seqlen, tokens.device)
+    nbytes = _LIB.xgpr_conv_feature_rows_workspace_bytes(radem.shape[2], int(conv_width) * table.shape[1], rows_out.shape[1], n)
+    ws, wp, wn = _workspace(nbytes, tokens.device)
+    return _lib.check(_LIB.xgpr_conv_token_rows_f32(
+        t, tab, zc, r, c, C.c_void_p(host.ctypes.data), C.c_void_p(dev.data_ptr()), n, tokens.shape[1], table.shape[0],
+        table.shape[1], rows_out.shape[1], chi.shape[0], radem.shape[2], host.shape[0], int(conv_width), int(scaling_type),
+        int(bool(fit_intercept)), wp, wn, _stream()))
+
+
+@_array_args("tokens", "table", "zrows", "grows", "radem", "chi")
+def hipConvTokenGradRows(tokens, table, zrows, grows, radem, chi, seqlen, sigma, conv_width, scaling_type, fit_intercept):
+    """hipConvGradRows for sequences given as tokens (xgpr_conv_token_grad_rows_f32): ``table`` is NOT pre-multiplied by
+    sigma; ``zrows`` and ``grows`` are OVERWRITTEN with exactly the rows hipConvGradRows writes for ``table[tokens]``."""
+    t = _dev(tokens, "tokens", torch.uint8, 2)
+    tab = _dev(table, "table", torch.float32, 2)
+    n = tokens.shape[0]
+    z = _float_rows(zrows, "zrows", n)
+    g = _float_rows(grows, "grows", n)
+    if tuple(grows.shape) != tuple(zrows.shape):
+        raise RuntimeError("Wrong array sizes.")
+    r = _radem3(radem)
+    c = _dev(chi, "chi", torch.float32, 1)
+    host, dev = _seqlens(seqlen, tokens.device)
+    nbytes = _LIB.xgpr_conv_grad_rows_workspace_bytes(radem.shape[2], int(conv_width) * table.shape[1], zrows.shape[1], n)
+    ws, wp, wn = _workspace(nbytes, tokens.device)
+    return _lib.check(_LIB.xgpr_conv_token_grad_rows_f32(
+        t, tab, z, g, r, c, C.c_void_p(host.ctypes.data), C.c_void_p(dev.data_ptr()), n, tokens.shape[1], table.shape[0],
+        table.shape[1], zrows.shape[1], chi.shape[0], radem.shape[2], host.shape[0], float(sigma), int(conv_width),
+        int(scaling_type), int(bool(fit_intercept)), wp, wn, _stream()))
+
+
 @_array_args("inputArr", "outputArr", "radem", "chiArr")
 def hipConv1dMaxpool(inputArr, outputArr, radem, chiArr, seqlengths, convWidth):
     """cudaConv1dMaxpool (xgpr_cuda_rfgen_cpp_ext.cpp:61-69); float32 output."""
@@ -819,3 +878,5 @@ cudaMiniARDGrad = hipMiniARDGrad
 cudaConv1dMaxpool = hipConv1dMaxpool
 cudaConv1dFGen = hipConv1dFGen
 cudaConvGrad = hipConvGrad
+cudaConvTokenRows = hipConvTokenRows
+cudaConvTokenGradRows = hipConvTokenGradRows
