@@ -378,6 +378,26 @@ int xgpr_zcache_matvec_scaled_f32(const float *zc, const double *v, double *w_ou
 int xgpr_zcache_zty_f32(const float *zc, const double *y, double *out, long n, long num_rffs, int fit_intercept,
                         double scale, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- the resident feature cache as IEEE binary16 rows (an opt-in MI355X-side mode, cache_features="half"; no reference
+ * counterpart, and not the reference's arithmetic).  The streaming matvec above is bound by the bytes of the float32 rows; the
+ * same rows rounded to binary16 are half the bytes: 16 KB per datapoint at 8192 features.
+ * Rounding contract: xgpr_rows_pack_f16 rounds each float32 value to the nearest binary16 value, ties to even, results in the
+ * binary16 subnormal range included -- a stored value differs from its source by at most max(2^-11 |z|, 2^-25); sources are
+ * finite and within the binary16 range (feature rows are).  `count` is the element count of one contiguous block of rows; rows
+ * 16-byte aligned, out 8-byte aligned.  It follows any float32 row writer of this library (xgpr_rbf_feature_cache_f32 at every
+ * width, xgpr_conv_feature_rows_f32, xgpr_conv_token_rows_f32), which makes each of them a source of binary16 rows.
+ * xgpr_zcache_matvec_f16 / xgpr_zcache_matvec_scaled_f16 are xgpr_zcache_matvec_f32 / _scaled_f32 with zc[i] read as binary16 and
+ * widened exactly: w_out = sum_i z_i (z_i . v), z_i = scale * widen(zc[i]) with Z[:,0] = 1 under fit_intercept; every product
+ * and sum in float64, partial slabs added in a fixed order, bit-reproducible.  The solve built on it is ridge regression on the
+ * rounded features.  num_rffs even, num_freqs <= 8192 (one tile of 1024 frequencies per wave; XGPR_ERR_UNSUPPORTED beyond);
+ * v and w_out 16-byte aligned, zc 4-byte aligned (16-byte loads are taken when num_rffs % 8 == 0 and zc is 16-byte aligned);
+ * workspace as for xgpr_ztz_matvec_f32. */
+int xgpr_rows_pack_f16(const float *rows, uint16_t *out, long count, void *stream);
+int xgpr_zcache_matvec_f16(const uint16_t *zc, const double *v, double *w_out, long n, long num_rffs,
+                           int fit_intercept, void *workspace, size_t workspace_bytes, void *stream);
+int xgpr_zcache_matvec_scaled_f16(const uint16_t *zc, const double *v, double *w_out, long n, long num_rffs,
+                                  double scale, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- SRHTCompressor.transform_x in one pass (srht_compressor.py:87-97: zero-pad the chunk to the padded
  * width, cudaSRHT in place, gather the sampled columns): out[i, c] = SRHT(z_i)[sampler[c]] for c < ncols,
  * z [n, m] and out [n, ldo] of the same type, radem int8 [padded_width], sampler int64 [>= ncols], all on the

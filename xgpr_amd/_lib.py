@@ -55,6 +55,9 @@ SIGNATURES = {
     "xgpr_rbf_feature_cache_f32": [_vp, _vp, _vp, _vp, _l, _l, _l, _l, _l, _vp, _sz, _vp],
     "xgpr_zcache_matvec_f32": [_vp, _vp, _vp, _l, _l, _i, _vp, _sz, _vp],
     "xgpr_zcache_matvec_scaled_f32": [_vp, _vp, _vp, _l, _l, _d, _vp, _sz, _vp],
+    "xgpr_rows_pack_f16": [_vp, _vp, _l, _vp],
+    "xgpr_zcache_matvec_f16": [_vp, _vp, _vp, _l, _l, _i, _vp, _sz, _vp],
+    "xgpr_zcache_matvec_scaled_f16": [_vp, _vp, _vp, _l, _l, _d, _vp, _sz, _vp],
     "xgpr_zcache_zty_f32": [_vp, _vp, _vp, _l, _l, _i, _d, _vp, _sz, _vp],
     "xgpr_zcache_block_matvec_f32": [_vp, _vp, _vp, _l, _l, _l, _i, _d, _i, _vp, _sz, _vp],
     "xgpr_zcache_block_project_f32": [_vp, _vp, _vp, _l, _l, _l, _i, _d, _vp, _sz, _vp],

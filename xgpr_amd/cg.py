@@ -136,7 +136,10 @@ class ConjugateGrad:
     def __init__(self, comm=SINGLE, cache_features=False):
         """``cache_features``: keep the shard's feature matrix resident in HBM as float32 and stream
         it each iteration instead of regenerating it (faster per iteration when it fits; off by
-        default -- the reference regenerates, and so does the benchmark's headline number)."""
+        default -- the reference regenerates, and so does the benchmark's headline number).  ``"half"`` (what
+        ``_resolve_cache_mode`` returns for a supported request): the resident rows are IEEE binary16
+        (``dataset.feature_cache_f16``) and every product with k <= 2 right-hand sides streams them; blocks of more
+        right-hand sides keep their float32 rows, regenerated -- this mode never builds the float32 cache."""
         self.comm = comm
         self.cache_features = cache_features
         self._ws = None
@@ -169,7 +172,12 @@ class ConjugateGrad:
         # NMLL probes, k = 26): the two contractions [n x M][M x k], [M x n][n x k] run on the
         # float64 matrix cores over float32 feature rows -- the resident cache, or windows of rows
         # regenerated into scratch (hipZCacheBlockMatvec).
-        if kernel.fused_ok() and vec.shape[1] <= 2:
+        if self._half and vec.shape[1] <= 2 and vec.is_cuda:
+            tmp = torch.empty(vec.shape[0], dtype=torch.float64, device=vec.device)
+            for j in range(vec.shape[1]):
+                self._ztz_half(dataset, kernel, vec[:, j].contiguous(), tmp)
+                matvec[:, j] = tmp
+        elif kernel.fused_ok() and vec.shape[1] <= 2:
             xs = dataset.scaled_x(kernel.hyperparams[1])
             if self._ws is None or self._ws.numel() < kernel.workspace_bytes() or self._ws.device != xs.device:
                 self._ws = torch.empty(kernel.workspace_bytes(), dtype=torch.uint8, device=xs.device)
@@ -208,7 +216,7 @@ class ConjugateGrad:
         if not vec.is_contiguous():
             vec = vec.contiguous()
         out = matvec if matvec.is_contiguous() else torch.zeros_like(vec)
-        if (self.cache_features or self._holds_seq_cache(dataset, kernel)) and dataset.get_local_ndatapoints() > 0:
+        if (self._wants_f32_cache or self._holds_seq_cache(dataset, kernel)) and dataset.get_local_ndatapoints() > 0:
             zc = dataset.feature_cache(kernel)
             kernel.ztz_block_cached(zc, vec, out, self._block_ws(zc.shape[0], kernel, k, vec.device))
         elif any_rows_ok(kernel, dataset):
@@ -259,7 +267,9 @@ class ConjugateGrad:
         if self._ws is None or self._ws.numel() < kernel.workspace_bytes() or self._ws.device != out.device:
             self._ws = torch.empty(kernel.workspace_bytes(), dtype=torch.uint8, device=out.device)
             self._ws_masks_of = None
-        if self._use_cache(kernel, dataset):
+        if self._half:
+            self._ztz_half(dataset, kernel, vec, out)
+        elif self._use_cache(kernel, dataset):
             kernel.ztz_matvec_cached(dataset.feature_cache(kernel), vec, out, self._ws)
         elif not kernel.fused_ok() and rows_matvec_ok(kernel, dataset):
             self._ztz_rows(dataset, kernel, vec, out)
@@ -274,12 +284,32 @@ class ConjugateGrad:
                 self._ws_masks_of = radem
         self.comm.all_reduce_(out)
 
+    @property
+    def _half(self):
+        """``cache_features="half"``: the k <= 2 products stream the binary16 cache."""
+        return isinstance(self.cache_features, str) and self.cache_features == "half"
+
+    @property
+    def _wants_f32_cache(self):
+        """Whether ``cache_features`` asks for the resident float32 cache (half mode does not: it must not build it)."""
+        return bool(self.cache_features) and not self._half
+
+    def _ztz_half(self, dataset, kernel, vec, out):
+        """out <- Z^T (Z vec) of this rank's rows for one right-hand side, streamed from the binary16 cache."""
+        if self._ws is None or self._ws.numel() < kernel.workspace_bytes() or self._ws.device != out.device:
+            self._ws = torch.empty(kernel.workspace_bytes(), dtype=torch.uint8, device=out.device)
+            self._ws_masks_of = None
+        if dataset.get_local_ndatapoints() == 0:
+            out.zero_()
+        else:
+            kernel.ztz_matvec_cached_f16(dataset.feature_cache_f16(kernel), vec, out, self._ws)
+
     def _use_cache(self, kernel, dataset=None):
-        """The resident cache when ``cache_features`` asks for it -- and, for the sequence kernels, when the dataset already
-        holds it at this sigma (their regenerated windows hold the same rows, at K k-mers x a SORF per sequence)."""
+        """The resident float32 cache when ``cache_features`` asks for it -- and, for the sequence kernels, when the dataset
+        already holds it at this sigma (their regenerated windows hold the same rows, at K k-mers x a SORF per sequence)."""
         if not (hasattr(kernel, "cache_ok") and kernel.cache_ok()):
             return False
-        return bool(self.cache_features) or self._holds_seq_cache(dataset, kernel)
+        return self._wants_f32_cache or self._holds_seq_cache(dataset, kernel)
 
     @staticmethod
     def _holds_seq_cache(dataset, kernel):
@@ -539,7 +569,7 @@ class ConjugateGrad:
         or (x_k, alphas, betas) with ``nmll_settings``."""
         dev = resid.device
         if (resid.shape[2] == 1 and not nmll_settings and dev.type == "cuda"
-                and (kernel.fused_ok() or rows_matvec_ok(kernel, dataset) or self._use_cache(kernel, dataset))
+                and (self._half or kernel.fused_ok() or rows_matvec_ok(kernel, dataset) or self._use_cache(kernel, dataset))
                 and (preconditioner is None or hasattr(preconditioner, "u_mat"))):
             return self._fit_one_rhs_device(dataset, kernel, preconditioner, resid, maxiter, tol, verbose, trace)
         if (self.BLOCK_DEVICE_SOLVE and 1 < resid.shape[2] <= 32 and dev.type == "cuda" and trace is None
@@ -609,11 +639,30 @@ class ConjugateGrad:
 SMALL_SHARD_ROWS = 200_000
 
 
+def refuse_half_cache(cache_features, who):
+    """The binary16 cache serves the one-right-hand-side regression solve only: ``who`` says so instead of silently taking
+    the float32 cache."""
+    if isinstance(cache_features, str) and cache_features == "half":
+        raise ValueError(f'{who} does not serve cache_features="half" (the binary16 cache is for the one-right-hand-side '
+                         'regression solve); pass "auto", True or False.')
+
+
 def _resolve_cache_mode(cache_features, kernel, dataset, block=False):
     """"auto": keep Z resident when the kernel supports it, when streaming it is faster than regenerating it
     (``kernel.cache_pays``; always for a block of right-hand sides) and the float32 cache of this shard fits
     comfortably in free HBM (it then needs cache + 2 GB with 1.5x headroom).  ``block``: the solve has
-    a block of right-hand sides (matrix-core matvec), which caches under ``block_ok``."""
+    a block of right-hand sides (matrix-core matvec), which caches under ``block_ok``.
+    "half": the resident rows as IEEE binary16 (half the bytes; the solve is ridge regression on the rounded features) --
+    returned as "half" when the kernel answers ``half_cache_ok()`` and the dataset has ``feature_cache_f16``.  A request
+    that cannot be served is answered as ``True`` is (the float32 cache): the convention for an unsupported cache request.
+    Solves with a block of right-hand sides do not serve the mode at all and raise ValueError."""
+    if isinstance(cache_features, str) and cache_features == "half":
+        if block:
+            refuse_half_cache(cache_features, "a solve with a block of right-hand sides")
+        supported = getattr(kernel, "half_cache_ok", None)
+        if supported is not None and supported() and hasattr(dataset, "feature_cache_f16"):
+            return "half"
+        return True
     if cache_features != "auto":
         return bool(cache_features)
     supported = getattr(kernel, "block_ok" if block else "cache_ok", None)
@@ -639,7 +688,10 @@ def cg_fit_lib_internal(kernel, dataset, cg_tol=1e-4, max_iter=500, precondition
     """cg_fitting_toolkit.py:18-70 -> (weights [M] f64 device, n_iter, losses).
     ``cache_features``: False = regenerate the features on every iteration (what the reference does);
     True = keep the shard's Z resident in HBM as float32 and stream it; "auto" (default) = resident
-    when it fits.  The solve is the same either way (same iteration count, weights to ~1e-9)."""
+    when it fits.  The solve is the same either way (same iteration count, weights to ~1e-9).
+    "half" (opt-in): the resident rows as IEEE binary16, half the bytes of True; the matvec then is that of the features
+    rounded to 11 significant bits (the right-hand side stays Z^T y of the float32 features), so the weights differ from the
+    other modes' by the effect of that rounding -- far below the random-feature approximation itself, but not 1e-9."""
     comm = dataset.comm
     cg_operator = ConjugateGrad(comm, _resolve_cache_mode(cache_features, kernel, dataset))
     resid = torch.zeros((kernel.get_num_rffs(), 2, 1), dtype=torch.float64, device=kernel.device)

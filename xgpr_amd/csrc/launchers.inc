@@ -900,6 +900,70 @@ int zcache_matvec_impl(const float *zc, const double *vec, double *w_out, long n
     return rc ? rc : reduce_slabs(a.wpart, w_out, num_rffs, nblocks * a.G, st);
 }
 
+// float32 rows -> binary16 rows (xgpr_rows_pack_f16): a grid of at most 8 workgroups per CU strides over the block
+int rows_pack_f16_impl(const float *rows, uint16_t *out, long count, void *stream) {
+    if (count <= 0) return fail(XGPR_ERR_NO_DATAPOINTS, "no datapoints");
+    if (!aligned16(rows) || (reinterpret_cast<uintptr_t>(out) & 7) != 0)
+        return fail(XGPR_ERR_WORKSPACE, "float32 rows must be 16-byte aligned and binary16 rows 8-byte aligned");
+    long nblocks = (count / 4 + 255) / 256;
+    if (nblocks < 1) nblocks = 1;
+    if (nblocks > 8L * device_cus()) nblocks = 8L * device_cus();
+    return launch(rows_pack_f16_kernel, dim3((unsigned)nblocks), dim3(256), 0, (hipStream_t)stream, "rows_pack_f16_kernel launch", rows, out, count);
+}
+
+int zcache_matvec_f16_impl(const uint16_t *zc, const double *vec, double *w_out, long n, long num_rffs, int fit_intercept,
+                           double scale_override, void *workspace, size_t wbytes, void *stream) {
+    if (n == 0) return fail(XGPR_ERR_NO_DATAPOINTS, "no datapoints");
+    if (num_rffs < 2 || (num_rffs & 1) != 0) return fail(XGPR_ERR_ODD_OUTPUT, "last dim of output must be even number");
+    const long F = num_rffs / 2;
+    if (F > 8192) return fail(XGPR_ERR_UNSUPPORTED, "cached matvec over binary16 rows supports num_freqs <= 8192");
+    if (!aligned16(vec) || !aligned16(w_out) || (reinterpret_cast<uintptr_t>(zc) & 3) != 0)
+        return fail(XGPR_ERR_WORKSPACE, "vector pointers must be 16-byte aligned, the binary16 cache 4-byte aligned");
+    const size_t need = (size_t)ZTZ_MAX_SLABS * num_rffs * sizeof(double);
+    if (!workspace || wbytes < need || !aligned16(workspace))
+        return fail(XGPR_ERR_WORKSPACE, "workspace too small (see xgpr_ztz_matvec_workspace_bytes)");
+    hipStream_t st = (hipStream_t)stream;
+    Zc16Args a = {};
+    a.zc = zc; a.vec = vec; a.wpart = reinterpret_cast<double *>(workspace);
+    a.n = n; a.F = F; a.nb = (int)((F + 1023) / 1024);
+    a.G = 8 / a.nb;                                // as zcache_matvec_impl: 8 waves per workgroup = 2 per SIMD
+    if ((long)a.G > n) a.G = (int)n;
+    a.fit_intercept = fit_intercept;
+    const double scale = scale_override > 0.0 ? scale_override : rbf_scale<float>(F, fit_intercept);
+    a.inv_scale = 1.0 / scale; a.scale2 = scale * scale;
+    const int waves = a.nb * a.G;
+    long nblocks = device_cus();
+    const long max_by_rows = (n + a.G - 1) / a.G;
+    if (nblocks > max_by_rows) nblocks = max_by_rows;
+    if (nblocks * a.G > ZTZ_MAX_SLABS) nblocks = ZTZ_MAX_SLABS / a.G;
+    // Rows start on a 4-byte boundary for every even num_rffs; a load is as wide as the row length and the base allow: FPL = 4 / 2 / 1
+    // frequencies (16 / 8 / 4 bytes).  RING datapoints in flight per wave, measured on one MI355X in one process with every candidate
+    // instantiated, five rounds of ten launches alternating with the float32 kernel (profiles/half_cache_sweep.json), ms per matvec,
+    // median (min .. max) -- float32 rows, zcache_ztz_kernel: 5.136 (5.127 .. 5.137) / 0.687 (0.686 .. 0.693) / 2.729 (2.723 .. 2.735):
+    //   FPL RING VGPRs | 1e6 x 8192            | 125 000 x 8192        | 250 000 x 16384
+    //    2   2   200   | 3.170 (3.160 .. 3.181) | 0.440 (0.438 .. 0.444) | 1.677 (1.620 .. 1.684)
+    //    2   3   216   | 3.033 (3.018 .. 3.048) | 0.401 (0.400 .. 0.404) | 1.568 (1.526 .. 1.577)
+    //    2   4   232   | 2.966 (2.954 .. 2.973) | 0.393 (0.387 .. 0.396) | 1.526 (1.494 .. 1.531)
+    //    2   5   248   | 2.924 (2.922 .. 2.932) | 0.386 (0.381 .. 0.395) | 1.500 (1.475 .. 1.505)
+    //    4   2   204   | 3.174 (3.161 .. 3.237) | 0.405 (0.404 .. 0.409) | 1.545 (1.542 .. 1.608)
+    //    4   3   220   | 2.823 (2.788 .. 2.830) | 0.368 (0.367 .. 0.373) | 1.448 (1.400 .. 1.450)
+    //    4   4   236   | 2.721 (2.715 .. 2.767) | 0.362 (0.358 .. 0.367) | 1.393 (1.381 .. 1.410)
+    //    4   5   252   | 2.708 (2.698 .. 2.709) | 0.357 (0.355 .. 0.367) | 1.376 (1.363 .. 1.391)
+    // (RING = 6 spills at every width.)  16-byte loads win at every depth from 3 on (v in planes: zcache_half.inc).  RING = 5 is 0.5 - 1.4 %
+    // ahead of 4 with overlapping ranges at two of the three shapes, four registers below the limit of two waves per SIMD; RING = 4
+    // keeps 20 registers of headroom and is what is built.  4-byte loads (odd num_freqs, or a base that is only 4-byte aligned) spend
+    // more registers on addresses: RING = 4 spills there, 3 does not (242 VGPRs).
+    const uintptr_t base = reinterpret_cast<uintptr_t>(zc);
+    const int fpl = (F % 4 == 0 && (base & 15) == 0) ? 4 : (F % 2 == 0 && (base & 7) == 0) ? 2 : 1;
+    const size_t lds = (size_t)a.nb * 1024 * 16 + 2 * 8 * 8 * sizeof(double);
+    const dim3 grid((unsigned)nblocks), block((unsigned)(waves * 64));
+    const char *what = "zcache16_ztz_kernel launch";
+    const int rc = fpl == 4 ? launch(zcache16_ztz_kernel<4, 4>, grid, block, lds, st, what, a)
+                 : fpl == 2 ? launch(zcache16_ztz_kernel<2, 4>, grid, block, lds, st, what, a)
+                            : launch(zcache16_ztz_kernel<1, 3>, grid, block, lds, st, what, a);
+    return rc ? rc : reduce_slabs(a.wpart, w_out, num_rffs, nblocks * a.G, st);
+}
+
 // z^T y over float32 feature rows (xgpr_zcache_zty_f32): ~8 workgroups per CU of 512 columns x a contiguous range of rows, partial
 // sums in slabs of the workspace (the matvec's ZTZ_MAX_SLABS x M doubles), added in slab order -- the geometry depends on n, M and the
 // device only, so the result is reproducible bit for bit

@@ -55,6 +55,7 @@ namespace {
 #include "wave_tile.inc"
 #include "fused_ztz.inc"
 #include "zcache.inc"
+#include "zcache_half.inc"
 #include "zblock.inc"
 #include "sketch_gemm.inc"
 #include "gram.inc"
@@ -439,6 +440,16 @@ int xgpr_zcache_matvec_scaled_f32(const float *zc, const double *v, double *w_ou
                                   void *workspace, size_t workspace_bytes, void *stream) {
     if (!(scale > 0.0)) return fail(XGPR_ERR_ARRAY_DIMS, "scale must be positive");
     return zcache_matvec_impl(zc, v, w_out, n, num_rffs, 0, scale, workspace, workspace_bytes, stream);
+}
+int xgpr_rows_pack_f16(const float *rows, uint16_t *out, long count, void *stream) { return rows_pack_f16_impl(rows, out, count, stream); }
+int xgpr_zcache_matvec_f16(const uint16_t *zc, const double *v, double *w_out, long n, long num_rffs, int fit_intercept,
+                           void *workspace, size_t workspace_bytes, void *stream) {
+    return zcache_matvec_f16_impl(zc, v, w_out, n, num_rffs, fit_intercept, 0.0, workspace, workspace_bytes, stream);
+}
+int xgpr_zcache_matvec_scaled_f16(const uint16_t *zc, const double *v, double *w_out, long n, long num_rffs, double scale,
+                                  void *workspace, size_t workspace_bytes, void *stream) {
+    if (!(scale > 0.0)) return fail(XGPR_ERR_ARRAY_DIMS, "scale must be positive");
+    return zcache_matvec_f16_impl(zc, v, w_out, n, num_rffs, 0, scale, workspace, workspace_bytes, stream);
 }
 int xgpr_zcache_zty_f32(const float *zc, const double *y, double *out, long n, long num_rffs, int fit_intercept, double scale,
                         void *workspace, size_t workspace_bytes, void *stream) {

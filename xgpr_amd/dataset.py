@@ -174,6 +174,34 @@ class DeviceDataset:
             self._zcache_key = key
         return self._zcache
 
+    HALF_WINDOW_BYTES = 1 << 30     # the float32 scratch window the binary16 cache is packed through
+
+    def feature_cache_f16(self, kernel):
+        """The feature cache of the whole shard for ``kernel`` at its current sigma as IEEE binary16 rows [n, num_rffs]
+        (``cache_features="half"``): the float32 rows of ``feature_cache`` rounded to nearest even, bit for bit.  Packed from
+        the resident float32 cache when the dataset holds it; otherwise regenerated window by window through one float32
+        scratch window of at most ``HALF_WINDOW_BYTES`` -- the float32 cache is never created here."""
+        from . import xgpr_hip_rfgen_ext as ext
+        from .cg import holds_cache, row_windows, shard_lengths
+        key = (id(kernel), float(kernel.hyperparams[1]))
+        if getattr(self, "_zcache16_key", None) != key:
+            self._zcache16 = None
+            n, m = self._xdata.shape[0], kernel.get_num_rffs()
+            zc16 = torch.empty((n, m), dtype=torch.float16, device=kernel.device)
+            if n > 0 and holds_cache(self, kernel):
+                ext.hipRowsToHalf(self._zcache, zc16)
+            elif n > 0:
+                xs = self.scaled_x(kernel.hyperparams[1])
+                # windows of a multiple of four rows: every window's binary16 rows then start on an 8-byte boundary
+                wbytes = self.HALF_WINDOW_BYTES // (16 * m) * (16 * m)
+                for lo, zc in row_windows(xs, kernel, None, wbytes, shard_lengths(self, kernel)):
+                    ext.hipRowsToHalf(zc, zc16[lo:lo + zc.shape[0]])
+            self._zcache16, self._zcache16_key = zc16, key
+        return self._zcache16
+
+    def feature_cache_f16_bytes(self, kernel):
+        return self._xdata.shape[0] * kernel.get_num_rffs() * 2
+
     def get_chunked_features(self, kernel, with_y=False, from_cache=False):
         """Chunks of the float64 feature matrix (``kernel.transform_x`` of each x chunk), optionally with the
         standardised y chunk.  ``from_cache``: widen rows of the resident float32 feature cache instead of

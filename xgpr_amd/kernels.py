@@ -205,6 +205,16 @@ class SORFKernel(KernelBase):
             self._cache_bws = torch.empty(need, dtype=torch.uint8, device=zcache.device)
         ext.hipZCacheBlockMatvec(zcache, vec[:, None], out[:, None], self.fit_intercept, self._cache_bws)
 
+    # ---- the resident cache as IEEE binary16 rows (cache_features="half", opt-in): half the bytes per iteration and per
+    # shard; the solve is ridge regression on the features rounded to 11 significant bits
+    def half_cache_ok(self):
+        """Whether the k <= 2 matvec can stream this kernel's rows rounded to binary16: a HIP device, ``rows_ok`` and one tile
+        per wave (num_freqs <= 8192)."""
+        return torch.device(self.device).type == "cuda" and self.rows_ok() and ext.half_cache_ok(self.num_freqs)
+
+    def ztz_matvec_cached_f16(self, zc16, vec, out, workspace):
+        ext.hipZCacheMatvecHalf(zc16, vec, out, self.fit_intercept, workspace)
+
     # ---- block of right-hand sides (approximate-NMLL probes, k = 26): float64 matrix cores over
     # the float32 cache, either the resident one or a window of rows regenerated into scratch
     def block_ok(self):
@@ -461,6 +471,14 @@ class ConvSORFKernel(KernelBase):
 
     def ztz_matvec_cached(self, zcache, vec, out, workspace):
         ext.hipZCacheMatvecScaled(zcache, vec, out, 1.0, workspace)
+
+    def half_cache_ok(self):
+        """Whether the k <= 2 matvec can stream this kernel's rows rounded to binary16 (cache_features="half")."""
+        return self.seq_rows_ok() and ext.half_cache_ok(self.num_freqs)
+
+    def ztz_matvec_cached_f16(self, zc16, vec, out, workspace):
+        """the rows are complete (intercept column included): the scaled entry with 1.0"""
+        ext.hipZCacheMatvecHalfScaled(zc16, vec, out, 1.0, workspace)
 
     def block_ok(self):
         return self.num_rffs % 4 == 0

@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from . import nmll as _nmll
-from .cg import cg_fit_lib_internal
+from .cg import cg_fit_lib_internal, refuse_half_cache
 from .classification import fit_classifier, predict_proba
 from .exact import calc_weights_exact, calc_variance_exact
 from .dataset import TokenBatch, token_batch
@@ -97,7 +97,9 @@ class xGPRegression(_ModelBase):
     def fit(self, dataset, preconditioner=None, tol=1e-6, max_iter=500, mode="cg", suppress_var=False,
             max_rank=3000, min_rank=512, autoselect_target_ratio=30., always_use_srht2=False, run_diagnostics=False,
             cache_features="auto"):
-        """xgp_regression.py:381-493."""
+        """xgp_regression.py:381-493.  ``cache_features``: "auto" (default), True, False as ``cg_fit_lib_internal``; "half"
+        (opt-in) keeps the CG solve's resident feature rows as IEEE binary16 -- half the memory and bytes per iteration, a
+        solve on features rounded to 11 significant bits."""
         self._initialize_kernel(dataset)
         self.trainy_mean, self.trainy_std = dataset.get_ymean(), dataset.get_ystd()
         self.weights = self.var = None
@@ -188,6 +190,7 @@ class xGPClassification(_ModelBase):
     def fit(self, dataset, preconditioner=None, tol=1e-3, max_iter=500, max_rank=3000, min_rank=512,
             autoselect_target_ratio=30., always_use_srht2=False, run_diagnostics=False, cache_features="auto"):
         """xgp_classification.py:111-200."""
+        refuse_half_cache(cache_features, "xGPClassification.fit")
         self._initialize_kernel(dataset)
         if preconditioner is None:
             preconditioner, _, _ = autoselect_preconditioner(

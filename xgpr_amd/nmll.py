@@ -26,7 +26,7 @@ import numpy as np
 import torch
 from scipy.linalg import eigh_tridiagonal
 
-from .cg import ConjugateGrad, _resolve_cache_mode, window_ranges
+from .cg import ConjugateGrad, _resolve_cache_mode, refuse_half_cache, window_ranges
 from .exact import calc_design_mat, direct_weight_calc
 from .preconditioner import RandNysPreconditioner
 
@@ -79,6 +79,7 @@ def approximate_nmll(kernel, dataset, preconditioner=None, manual_settings=None,
     preconditioner given one is built from ``manual_settings`` merged over the reference defaults
     (the reference's rank autoselection is outside the path; pass a preconditioner to control it).
     ``details``: optional dict that receives alphas, betas, logdet, the weights and the iteration count."""
+    refuse_half_cache(cache_features, "approximate_nmll")
     settings = dict(DEFAULT_NMLL_PARAMS)
     if manual_settings is not None:
         for key in settings:

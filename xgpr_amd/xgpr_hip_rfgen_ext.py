@@ -781,6 +781,51 @@ def hipZCacheMatvec(cacheArr, vec, outVec, fitIntercept, workspace):
         C.c_void_p(workspace.data_ptr()), C.c_size_t(workspace.numel()), _stream()))
 
 
+HALF_CACHE_MAX_FREQS = 8192     # the streaming matvec over binary16 rows: one tile of 1024 frequencies per wave (include/xgpr_hip.h)
+
+
+def half_cache_ok(num_freqs):
+    """Whether hipZCacheMatvecHalf serves rows of ``num_freqs`` frequencies."""
+    return 1 <= int(num_freqs) <= HALF_CACHE_MAX_FREQS
+
+
+def hipRowsToHalf(rows_f32, out_f16):
+    """out_f16 <- rows_f32 rounded to IEEE binary16 (round to nearest even, subnormals kept); both [n, num_rffs] (or any
+    equal shape), contiguous.  Any float32 row writer followed by this is a source of binary16 rows."""
+    if not isinstance(rows_f32, torch.Tensor) or not isinstance(out_f16, torch.Tensor):
+        raise TypeError("rows_f32 / out_f16: expected device arrays")
+    src = _dev(rows_f32, "rows_f32", torch.float32, rows_f32.dim())
+    dst = _dev(out_f16, "out_f16", torch.float16, out_f16.dim())
+    if tuple(rows_f32.shape) != tuple(out_f16.shape):
+        raise TypeError("out_f16: expected the shape of rows_f32")
+    return _lib.check(_LIB.xgpr_rows_pack_f16(src, dst, rows_f32.numel(), _stream()))
+
+
+def hipZCacheMatvecHalfScaled(cache_f16, vec, out, scale, workspace):
+    """``Z.T @ (Z @ vec)`` with Z = scale * cache_f16 widened exactly (any kernel's feature rows rounded to binary16)."""
+    zc = _dev(cache_f16, "cache_f16", torch.float16, 2)
+    v = _dev(vec, "vec", torch.float64, 1)
+    o = _dev(out, "out", torch.float64, 1)
+    if vec.shape[0] != cache_f16.shape[1] or out.shape[0] != cache_f16.shape[1]:
+        raise TypeError("vec / out: expected num_rffs entries")
+    return _lib.check(_LIB.xgpr_zcache_matvec_scaled_f16(
+        zc, v, o, cache_f16.shape[0], cache_f16.shape[1], float(scale),
+        C.c_void_p(workspace.data_ptr()), C.c_size_t(workspace.numel()), _stream()))
+
+
+def hipZCacheMatvecHalf(cache_f16, vec, out, fitIntercept, workspace):
+    """``Z.T @ (Z @ vec)`` streamed from the resident binary16 feature cache: hipZCacheMatvec over rows rounded by
+    hipRowsToHalf (the RBF-family scale, Z[:, 0] = 1 under fitIntercept); float64 products and sums, deterministic."""
+    zc = _dev(cache_f16, "cache_f16", torch.float16, 2)
+    v = _dev(vec, "vec", torch.float64, 1)
+    o = _dev(out, "out", torch.float64, 1)
+    if vec.shape[0] != cache_f16.shape[1] or out.shape[0] != cache_f16.shape[1]:
+        raise TypeError("vec / out: expected num_rffs entries")
+    return _lib.check(_LIB.xgpr_zcache_matvec_f16(
+        zc, v, o, cache_f16.shape[0], cache_f16.shape[1], int(bool(fitIntercept)),
+        C.c_void_p(workspace.data_ptr()), C.c_size_t(workspace.numel()), _stream()))
+
+
 def hipZCacheZtY(cacheArr, yvec, outVec, fitIntercept, workspace, scale=0.0):
     """``outVec = Z.T @ yvec`` from float32 feature rows (exact_nmll_calcs.py:35-37 without float64 Z): Z = scale *
     cacheArr with Z[:, 0] = 1 under fitIntercept; scale = 0 selects the RBF-family scale, a positive scale is for caches
@@ -880,3 +925,6 @@ cudaConv1dFGen = hipConv1dFGen
 cudaConvGrad = hipConvGrad
 cudaConvTokenRows = hipConvTokenRows
 cudaConvTokenGradRows = hipConvTokenGradRows
+cudaRowsToHalf = hipRowsToHalf
+cudaZCacheMatvecHalf = hipZCacheMatvecHalf
+cudaZCacheMatvecHalfScaled = hipZCacheMatvecHalfScaled
