@@ -466,7 +466,11 @@ int xgpr_cross_gram_f64(const float *a, const float *b, long n, long num_rffs, d
  * features out[n, num_rffs] and their gradient grad[n, num_rffs, num_lengthscales] w.r.t. the per-group
  * inverse lengthscales, from the dense precomputed weights[num_freqs, d]; sigma_map[d] int32 (group of each
  * input feature), sigma_vals[d] float64, all on the device.  fit_intercept only selects the constant; the
- * caller sets column 0 (kernel_baseclass.py:356-359).  Up to 8 groups; n <= 262140 per call. */
+ * caller sets column 0 (kernel_baseclass.py:356-359).  Up to 8 groups; n <= 262140 per call.
+ * Precondition: every sigma_map[k] lies in [0, num_lengthscales).  The map lives on the device and is NOT validated: a column
+ * whose entry is outside that range still enters the features through sigma_vals[k], but is accumulated into no group's
+ * gradient (no error is reported).  Every element of out and grad is written (grad is not accumulated into): a group that no
+ * column belongs to gets zeros.  x, weights: any element-aligned address (no vector loads). */
 int xgpr_mini_ard_grad_f32(const float *x, double *out, const float *weights, const int32_t *sigma_map,
                            const double *sigma_vals, double *grad, long n, long d, long out_rows,
                            long num_rffs, long num_freqs, long w_cols, long map_len, long sig_len,

@@ -20,6 +20,12 @@ Definitions (x a row of ``width`` numbers, zero-padded to P; radem[3, 1, R] sign
                for scaling 0, 1, 2; the gradient is the same sum of the per-window gradient terms
     max-pool   out[f] = max(0, max_w p_w[f]) stored as float32
     SRHT       y = H_P (x * radem) 2^(-k/2);    bare FHT  y = H_P x   (2-D rows, or every row of a 3-D array)
+    MiniARD    W[j, k] = projection of the unit row e_k at frequency j (a dense [F, d] matrix); sigma_map[k] the lengthscale
+               group of input column k, sigma_vals[k] the inverse lengthscale of that column, nl the number of groups:
+                   a[i, j]   = sum_k sigma_vals[k] x[i, k] W[j, k]
+                   G_l[i, j] = sum_{k: sigma_map[k] = l} x[i, k] W[j, k]
+               features out[i, 2 j] = c cos a, out[i, 2 j + 1] = c sin a;
+               grad[i, 2 j, l] = -G_l c sin a,  grad[i, 2 j + 1, l] = G_l c cos a       (grad is [n, 2 F, nl])
 
 ``mistake=`` arguments exist for the sensitivity test only (tests/test_dense_reference_cpu.py): each plants ONE
 structural error in the definition above, so that the test can show the chosen shapes would expose it.
@@ -156,6 +162,57 @@ def rbf_grad(x, radem, chi, sigma, intercept, mistake=None, proj=None):
     return _interleave(np.cos(a) * c, np.sin(a) * c), _interleave(-np.sin(a) * p * c, np.cos(a) * p * c)
 
 
+def mini_ard_weights(d, radem, chi, by_definition=False):
+    """W[F, d] of the MiniARD gradient operator: W[j, k] is the projection of the unit row e_k at frequency j, that is
+    ``projections(np.eye(d), radem, chi).T`` (``by_definition=True`` computes exactly that).  By default the same numbers row by row
+    instead of column by column: with S = c^3 H D2 H D1 H D0 the SORF matrix of a repetition (c = 2^(-k/2), D_s the sign diagonals),
+    (S e_k)[j] = (S^T e_j)[k] and S^T = c^3 D0 H D1 H D2 H -- F transforms of unit rows instead of d of them (d = 2049 pads to 4096;
+    the test of this module compares the two forms at the smaller shapes)."""
+    d = int(d)
+    if by_definition:
+        return projections(np.eye(d), radem, chi).T
+    F, P = chi.shape[0], padded_width(d)
+    out = np.zeros((F, d), dtype=LD)
+    scale = np.sqrt(LD(1) / LD(P))
+    for rep in range(ceil(F / P)):
+        off = rep * P
+        m = min(P, F - off)
+        y = np.eye(P, dtype=LD)[:m]
+        for s in (2, 1, 0):
+            y = apply_hadamard(y) * scale * radem[s, 0, off:off + P].astype(LD)
+        out[off:off + m] = np.asarray(chi[off:off + m], dtype=LD)[:, None] * y[:, :d]
+    return out
+
+
+def mini_ard_grad(x, W, sigma_map, sigma_vals, intercept, nl, mistake=None):
+    """-> (features [n, 2F], grad [n, 2F, nl]); sigma_map[d] the group of every input column, sigma_vals[d] its sigma."""
+    x, W = np.asarray(x, dtype=LD), np.asarray(W, dtype=LD)
+    smap, sv = np.asarray(sigma_map, dtype=np.int64), np.asarray(sigma_vals, dtype=LD)
+    n, d = x.shape
+    F = W.shape[0]
+    if mistake == "group_edge":                         # every column takes the group of its left neighbour
+        smap = np.concatenate([smap[:1], smap[:-1]])
+    if mistake == "drop_last":
+        x = x.copy()
+        x[:, d - 1] = 0
+    c = rbf_scale(F, intercept and mistake != "no_half")
+    a = (x * sv) @ W.T
+    cs, sn = np.cos(a) * c, np.sin(a) * c
+    if mistake == "swap_partner":
+        cs, sn = sn, cs
+    group = np.zeros((nl, n, F), dtype=LD)
+    for l in range(nl):
+        xl = x * (smap == l)
+        group[l] = (xl * sv if mistake == "sigma_in_grad" else xl) @ W.T
+    if mistake == "layout":
+        grad = np.stack([_interleave(-group[l] * sn, group[l] * cs) for l in range(nl)], axis=1).reshape(n, 2 * F, nl)
+    else:
+        grad = np.stack([_interleave(-group[l] * sn, group[l] * cs) for l in range(nl)], axis=2)
+    if mistake == "swap_partner":
+        cs, sn = sn, cs
+    return _interleave(cs, sn), grad
+
+
 def _windows(seq, seqlen, conv_width, mistake=None):
     """[nkmers, conv_width * C]: the first seqlen - conv_width + 1 windows of one sequence [L, C]."""
     nk = int(seqlen) - conv_width + 1
@@ -258,6 +315,20 @@ def deinterleaved(out):
 # * products with a vector: t = Z v, w = Z^T t with |dZ| <= cz elementwise, |Z| <= zmax:  |dt| <= cz ||v||_1,
 #   |t| <= zmax ||v||_1, |dw| <= n (cz (|t| + |dt|) + zmax |dt|), plus the float64 dot products of the one who forms them
 #   ((n + m) u64 n zmax^2 ||v||_1).
+# * MiniARD gradient operator (no butterflies: a dense product with the given W, which operator and reference receive alike).
+#   Documented arithmetic: every product x_ik W_jk is rounded once in the type T (u); the product with sigma_k, both sums over
+#   k and cos / sin are float64; the constant c is rounded to T and then multiplied in float64; G s is rounded once in float64.
+#   With A = max_ij sum_k |sigma_k x_ik W_jk| and B = max_ijl sum_{k in l} |x_ik W_jk| (from the reference's own inputs):
+#   - argument: term k carries (1 + d_k)(1 + t_k), |d_k| <= u, |t_k| <= (1 + u64)^d - 1 (one rounding for sigma_k *, at most d - 1
+#     for the additions), and (1 + u)(1 + u64)^d - 1 <= (u + (d + 1) u64)(1 + u) while d^2 u64 <= 1:
+#         da = (u + (d + 1) u64) (1 + u) A
+#   - group sum: the same without the product with sigma:      dG = (u + d u64) (1 + u) B
+#   - c cos a, c sin a: the trigonometric value is within da (1-Lipschitz) + 2 LIBM_ULPS u64 (library), |value| <= 1; the
+#     constant is c (1 + d), |d| <= u; the float64 product adds u64:
+#         ds = c ((1 + u) (da + 2 LIBM_ULPS u64 + u64) + u)
+#   - gradient: the product of the two computed factors |s^| <= c + ds, |G^| <= B + dG, rounded once in float64:
+#         dg = (c + ds) dG + B ds + u64 (c + ds) (B + dG)
+#   - where longdouble cannot be taken as exact its own d-term dot products (gamma_d A, gamma_d B) are added to da and dG.
 # Every cap is the maximum over rows / windows (largest norm) and frequencies (largest |chi|): one number per case.
 # ------------------------------------------------------------------------------------------------------------------
 
@@ -343,6 +414,28 @@ def cap_rbf(dtype, x, chi, intercept, u_out=0.0):
 def cap_rbf_grad(dtype, x, chi, sigma, intercept, pmax):
     F, P = chi.shape[0], padded_width(x.shape[1])
     return cap_grad(dtype, P, max_row_norm(x), float(np.abs(chi).max()), float(rbf_scale(F, intercept)), float(sigma), pmax)
+
+
+def mini_ard_sums(x, W, sigma_map, sigma_vals, nl):
+    """A = max_ij sum_k |sigma_k x_ik W_jk|,  B = max_ijl sum_{k in l} |x_ik W_jk|."""
+    ax, aw = np.abs(np.asarray(x, dtype=LD)), np.abs(np.asarray(W, dtype=LD))
+    smap = np.asarray(sigma_map, dtype=np.int64)
+    big_a = float(((ax * np.abs(np.asarray(sigma_vals, dtype=LD))) @ aw.T).max())
+    big_b = max(float(((ax * (smap == l)) @ aw.T).max()) for l in range(nl))
+    return big_a, big_b
+
+
+def cap_mini_ard(dtype, x, W, sigma_map, sigma_vals, intercept, nl):
+    """-> (cap of the features, cap of the gradient) of the MiniARD gradient operator."""
+    u, d = unit_roundoff(dtype), x.shape[1]
+    c = float(rbf_scale(W.shape[0], intercept))
+    big_a, big_b = mini_ard_sums(x, W, sigma_map, sigma_vals, nl)
+    own = 0.0 if LD_EPS < 2e-19 else (d + 2) * ULD / (1 - (d + 2) * ULD)
+    da = (u + (d + 1) * U64) * (1 + u) * big_a + own * big_a
+    dG = (u + d * U64) * (1 + u) * big_b + own * big_b
+    ds = c * ((1 + u) * (da + 2 * LIBM_ULPS * U64 + U64) + u)
+    dg = (c + ds) * dG + big_b * ds + U64 * (c + ds) * (big_b + dG)
+    return ds, dg
 
 
 def _conv_case(x, seqlen, chi, conv_width):

@@ -35,6 +35,15 @@ DISPATCH_LG = range(1, 14)
 DISPATCH_FIXED = [(3, d, 4096 if lg <= 10 else 2 << lg) for lg in DISPATCH_LG for d in (1 << lg, max(1, (1 << lg) - 1))]
 DISPATCH_SEQ = [(3, 3, d, 1, rffs) for _, d, rffs in DISPATCH_FIXED]
 DISPATCH_SEQLEN = (1, 2, 3)
+# MiniARD gradient operator, (n, d, F, nl, map kind).  The HIP kernel tiles 64 frequencies x 4 datapoints and stages d in slices of
+# 64: d and F below, at and above one slice / tile (63, 64, 65), two slices and a bit (129 x 130), several blocks both ways (9 x 192),
+# the smallest problem, and the widest d of the fixture test; one group, the most the kernel unrolls (8), groups in blocks, interleaved
+# (k % nl), in blocks of uneven sizes with groups of one column on both sides of the slice edges 64 and 128, and a map that
+# never takes one of its values.
+ARD = [(1, 1, 1, 1, "block"), (5, 63, 63, 2, "block"), (4, 64, 64, 8, "interleaved"), (6, 65, 65, 3, "block"),
+       (3, 129, 130, 8, "uneven"), (9, 200, 192, 5, "interleaved"), (3, 128, 70, 4, "absent"), (2, 2049, 48, 3, "block")]
+ARD_UNEVEN_SPLITS = (1, 3, 64, 65, 100, 127, 128)        # d = 129, eight groups of 1, 2, 61, 1, 35, 27, 1, 1 columns
+ARD_ABSENT = 2
 
 
 def _signs(rng, size):
@@ -94,6 +103,60 @@ class SeqCase:
 
     def __repr__(self):
         return f"seq(n={self.n}, L={self.L}, C={self.C}, cw={self.cw}, rffs={self.rffs})"
+
+
+class ArdCase:
+    """x: float32 values of row norm about 1; sigma per group in [0.5, 2], none of them 1 (0.5 + 1.5 (r + 1/2) / nl, r a seeded
+    permutation of the groups); W from the definition with seeded signs and chi, rounded to the type under test so that operator
+    and reference receive the same weights (``typed``); one dense reference per type and intercept setting, computed once."""
+
+    def __init__(self, n, d, F, nl, kind):
+        rng = np.random.default_rng([n, d, F, nl])
+        self.n, self.d, self.F, self.nl, self.kind, self.rffs = n, d, F, nl, kind, 2 * F
+        self.P = dr.padded_width(d)
+        self.x = (rng.standard_normal((n, d)) / np.sqrt(d)).astype(np.float32)
+        self.radem = _signs(rng, (3, 1, ceil(F / self.P) * self.P))
+        self.chi = np.sqrt(rng.chisquare(self.P, size=F)).astype(np.float32)
+        cols = np.arange(d)
+        if kind == "block":
+            smap = cols * nl // d
+        elif kind == "interleaved":
+            smap = cols % nl
+        elif kind == "uneven":
+            assert d == 129 and nl == len(ARD_UNEVEN_SPLITS) + 1
+            smap = np.searchsorted(np.asarray(ARD_UNEVEN_SPLITS), cols, side="right")
+        else:
+            assert kind == "absent" and nl > ARD_ABSENT + 1
+            present = np.asarray([g for g in range(nl) if g != ARD_ABSENT])
+            smap = present[cols * (nl - 1) // d]
+        self.sigma_map = smap.astype(np.int32)
+        self.sigma = 0.5 + 1.5 * (rng.permutation(nl) + 0.5) / nl
+        self.sigma_vals = self.sigma[self.sigma_map].astype(np.float64)
+        self.weights = dr.mini_ard_weights(d, self.radem, self.chi)
+        self._refs = {}
+
+    def typed(self, dtype):
+        return self.x.astype(dtype), np.ascontiguousarray(self.weights.astype(dtype))
+
+    def ref(self, dtype, icpt, mistake=None):
+        """-> (features, grad) of the dense reference for the weights as the type under test holds them."""
+        key = (np.dtype(dtype), bool(icpt), mistake)
+        if key not in self._refs:
+            x, w = self.typed(dtype)
+            self._refs[key] = dr.mini_ard_grad(x, w, self.sigma_map, self.sigma_vals, icpt, self.nl, mistake)
+        return self._refs[key]
+
+    def caps(self, dtype, icpt):
+        x, w = self.typed(dtype)
+        return dr.cap_mini_ard(dtype, x, w, self.sigma_map, self.sigma_vals, icpt, self.nl)
+
+    def __repr__(self):
+        return f"ard(n={self.n}, d={self.d}, F={self.F}, nl={self.nl}, {self.kind})"
+
+
+@functools.lru_cache(maxsize=None)
+def ard_case(n, d, F, nl, kind):
+    return ArdCase(n, d, F, nl, kind)
 
 
 @functools.lru_cache(maxsize=None)
@@ -258,6 +321,111 @@ def test_oracle_conv_grad(orc, n, L, C, cw, rffs, dtype):
         assert maxerr(of, rf) <= capf and maxerr(og, rg) <= capg
 
 
+def oracle_mini_ard(orc, case, dtype, icpt):
+    x, w = case.typed(dtype)
+    out, grad = np.zeros((case.n, case.rffs)), np.zeros((case.n, case.rffs, case.nl))
+    orc.cpuMiniARDGrad(x, out, w, case.sigma_map, case.sigma_vals, grad, icpt)
+    return out, grad
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+@pytest.mark.parametrize("icpt", [False, True])
+@pytest.mark.parametrize("n,d,F,nl,kind", ARD)
+def test_oracle_mini_ard_grad(orc, n, d, F, nl, kind, icpt, dtype):
+    case = ard_case(n, d, F, nl, kind)
+    rf, rg = case.ref(dtype, icpt)
+    of, og = oracle_mini_ard(orc, case, dtype, icpt)
+    capf, capg = case.caps(dtype, icpt)
+    report(f"mini_ard.f i={int(icpt)}", case, dtype, maxerr(of, rf), capf)
+    report(f"mini_ard.g i={int(icpt)}", case, dtype, maxerr(og, rg), capg)
+    assert maxerr(of, rf) <= capf and maxerr(og, rg) <= capg
+
+
+@pytest.mark.parametrize("n,d,F,nl,kind", [c for c in ARD if c[1] <= 200])
+def test_mini_ard_weights_row_form_equals_the_definition(n, d, F, nl, kind):
+    """mini_ard_weights builds W row by row (S^T e_j); the definition, projections of the unit rows e_k, column by column.  Both
+    are three rounds of dense longdouble products of length P and one product with chi on unit vectors: each within
+    3 (P + 2) u_ld chi_max of the exact numbers."""
+    case = ard_case(n, d, F, nl, kind)
+    by_def = dr.mini_ard_weights(d, case.radem, case.chi, by_definition=True)
+    assert case.weights.shape == by_def.shape == (F, d)
+    assert maxerr(case.weights, by_def) <= 2 * 3 * (case.P + 2) * dr.ULD * float(case.chi.max())
+
+
+# (d, num_rffs, split points): F = 33 is no multiple of P = 32; two full blocks of P = 64; d = P = 64 with eight groups
+ARD_KERNELS = [(20, 66, [7]), (50, 256, [10, 30]), (64, 128, [1, 2, 3, 4, 5, 6, 7])]
+
+
+def ard_weight_cap(dtype, d, chi, ref):
+    """The kernel objects build W by three float64 FHT rounds on the identity (rows of norm 1) and one product with chi, then store
+    it in their own type: the float64 projection cap, plus one rounding to float32 where that is the type."""
+    cap = dr._projection_cap(dr.U64, dr.padded_width(d), 1.0, float(np.abs(chi).max()))
+    return cap if np.dtype(dtype) == np.float64 else cap + dr.U32 * (float(np.abs(ref).max()) + cap)
+
+
+@pytest.mark.parametrize("dp", [False, True])
+@pytest.mark.parametrize("d,rffs,splits", ARD_KERNELS)
+def test_oracle_mini_ard_precomputed_weights(orc, d, rffs, splits, dp):
+    from oracle import oracle as omod
+    kern = omod.OracleMiniARDKernel(rffs, (10, d), splits, None, 123, double_precision=dp, ops=orc)
+    kern.precompute_weights()
+    dtype = np.float64 if dp else np.float32
+    assert kern.precomputed_weights.dtype == dtype and kern.precomputed_weights.shape == (rffs // 2, d)
+    ref = dr.mini_ard_weights(d, kern.radem_diag, kern.chi_arr)
+    err, cap = maxerr(kern.precomputed_weights, ref), ard_weight_cap(dtype, d, kern.chi_arr, ref)
+    report("mini_ard.W", (d, rffs), dtype, err, cap)
+    assert err <= cap
+
+
+# The NMLL gradient of a MiniARD kernel (shared with tests/test_gpu_mini_ard.py): n = 300, d = 12, three groups, 128 RFFs
+NMLL_ARD = dict(n=300, d=12, splits=[4, 9], rffs=128, chunk=128, hparams=np.array([0.45, 0.8, 1.3, 0.6]), eps=1e-3)
+
+
+def nmll_ard_problem():
+    p = NMLL_ARD
+    rng = np.random.default_rng(300)
+    x = rng.uniform(-1, 1, size=(p["n"], p["d"])).astype(np.float32).astype(np.float64)
+    y = np.sin(2 * x[:, 0]) + x[:, 5] * x[:, 6] + 0.5 * x[:, 10] + 0.1 * rng.standard_normal(p["n"])
+    return x, y
+
+
+def central_difference(fun, hparams, eps):
+    """d fun / d log(hparams[i]) by central differences of width eps in log space."""
+    out = np.zeros(hparams.shape[0])
+    for i in range(hparams.shape[0]):
+        up, down = np.log(hparams), np.log(hparams)
+        up[i] += eps
+        down[i] -= eps
+        out[i] = (fun(np.exp(up)) - fun(np.exp(down))) / (2 * eps)
+    return out
+
+
+def test_oracle_mini_ard_nmll_gradient_against_central_difference(orc):
+    """The oracle's exact_nmll_gradient of a multi-lengthscale kernel against a central difference of its exact_nmll in every
+    hyperparameter (lambda included), float64 kernel.  The printed deviation is the difference quotient's own error (its
+    truncation error, eps^2 / 6 times the third derivative): tests/test_gpu_mini_ard.py takes its tolerance from it.  Asserted
+    here: the deviation stays within twice the change of the quotient itself from eps to eps / 2 (which is 3/4 of the truncation
+    error at eps), plus the rounding of the quotient, 1e-12 |nmll| / eps."""
+    from oracle import oracle as omod
+    p = NMLL_ARD
+    x, y = nmll_ard_problem()
+    ds = omod.OracleDataset(x, y, None, chunk_size=p["chunk"])
+
+    def kernel(hp):
+        return omod.OracleMiniARDKernel(p["rffs"], x.shape, p["splits"], hp, 123, double_precision=True, ops=orc)
+
+    def value(hp):
+        return omod.exact_nmll(kernel(hp), ds)
+
+    nll, grad = omod.exact_nmll_gradient(kernel(p["hparams"]), ds)
+    assert np.isclose(nll, value(p["hparams"]), rtol=1e-12)
+    fd, fd_half = central_difference(value, p["hparams"], p["eps"]), central_difference(value, p["hparams"], p["eps"] / 2)
+    dev = np.abs(grad - fd)
+    print(f"NMLLFD mini_ard oracle: gradient {grad}  central difference {fd}")
+    print(f"NMLLFD mini_ard oracle: largest absolute deviation {dev.max():.3e}  largest relative deviation {(dev / np.abs(fd)).max():.3e}")
+    assert np.all(dev <= 2 * np.abs(fd - fd_half) + 1e-12 * abs(nll) / p["eps"]), (dev, np.abs(fd - fd_half))
+
+
 # ---------------------------------------------------------------------------------------------------- the dispatch shapes
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])
 @pytest.mark.parametrize("icpt", [False, True])
@@ -403,6 +571,38 @@ def test_sensitivity_sequences(n, L, C, cw, rffs):
             if grad_too:
                 bg = dr.conv_grad(case.x, case.seqlen, case.radem, case.chi, SIGMA, cw, 1, proj=case.proj)[1]
                 _assert_moved("convgrad sc=2", case, "scaling1for2", gref[1], bg, {dt: c[1] for dt, c in gcaps.items()})
+
+
+# MiniARD gradient operator (features f, gradient g).  Which planted mistake applies where, and on which output it is asserted:
+#   group_edge    every column takes its left neighbour's group   g; more than one group (nl > 1)
+#   drop_last     column d - 1 left out of the sums                f and g; every shape (at d = 1 nothing is left: a = 0, G = 0)
+#   sigma_in_grad G_l weighted by sigma                            g; every shape (no sigma is 1)
+#   swap_partner  the gradient's cos and sin partners exchanged    g; every shape
+#   layout        grad laid out [n, nl, 2F], then reshaped         g; nl > 1
+#   no_half       sqrt(1/F) with the intercept                     f; with the intercept.  (The gradient changes by the same
+#                 relative 1/(4F), but G is a signed sum while its cap grows with the sum of magnitudes B: not asserted there.)
+ARD_MISTAKES = {"group_edge": "g", "drop_last": "fg", "sigma_in_grad": "g", "swap_partner": "g", "layout": "g", "no_half": "f"}
+
+
+def ard_mistake_applies(mistake, case, icpt):
+    if mistake in ("group_edge", "layout"):
+        return case.nl > 1
+    return icpt if mistake == "no_half" else True
+
+
+@pytest.mark.parametrize("n,d,F,nl,kind", ARD)
+def test_sensitivity_mini_ard(n, d, F, nl, kind):
+    case = ard_case(n, d, F, nl, kind)
+    for icpt in (False, True):
+        for mistake, where in ARD_MISTAKES.items():
+            if not ard_mistake_applies(mistake, case, icpt):
+                continue
+            for dtype in (np.float32, np.float64):         # each type has its own weights, hence its own reference
+                (rf, rg), (bf, bg), (capf, capg) = case.ref(dtype, icpt), case.ref(dtype, icpt, mistake), case.caps(dtype, icpt)
+                if "f" in where:
+                    _assert_moved(f"ard.f i={int(icpt)}", case, mistake, rf, bf, {dtype: capf})
+                if "g" in where:
+                    _assert_moved(f"ard.g i={int(icpt)}", case, mistake, rg, bg, {dtype: capg})
 
 
 # ---------------------------------------------------------------------------------------------------- g19: the reference's slow path
