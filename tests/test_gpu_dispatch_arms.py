@@ -22,7 +22,8 @@ import torch
 import dense_reference as dr
 from test_dense_reference_cpu import (DISPATCH_FIXED, DISPATCH_SCALING, DISPATCH_SEQ, DISPATCH_SEQLEN, GRAD_SCALE, SIGMA, fixed_case,
                                       oracle_conv, oracle_conv_grad, oracle_maxpool, oracle_rbf, oracle_rbf_grad, seq_case)
-from test_gpu_dense_reference import BOTH, DEV, check, dev, host
+from guarded import Arena, Plain, patched_workspaces
+from test_gpu_dense_reference import BOTH, DEV, check, host
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -36,62 +37,78 @@ def ext():
 
 
 # ---------------------------------------------------------------------------------------------- what the device computes
-def run_fixed(ext, case, icpt):
-    """Every fixed-vector operator that serves the case's width -> {name: host array}."""
-    n, rffs, radem, out = case.n, case.rffs, dev(case.radem), {}
+def run_fixed(ext, case, icpt, alloc=None):
+    """Every fixed-vector operator that serves the case's width -> {name: host array}.  ``alloc`` supplies the arrays (tests/guarded.py:
+    separately allocated tensors by default, or a guarded arena)."""
+    alloc = alloc or Plain(DEV)
+    inp = lambda a, name: alloc.inp(torch.from_numpy(np.ascontiguousarray(a)), name=name)
+    n, rffs, radem, out = case.n, case.rffs, inp(case.radem, "radem"), {}
     for dtype in BOTH:
-        x, chi = (dev(a) for a in case.typed(dtype))
+        x, chi = (inp(a, nm) for a, nm in zip(case.typed(dtype), ("x", "chi")))
         tag = np.dtype(dtype).name
-        o = torch.full((n, rffs), 7.0, dtype=torch.float64, device=DEV)
+        o = alloc.out((n, rffs), torch.float64, fill=7.0, name=f"rbf.{tag}")
         ext.hipRBFFeatureGen(x, o, radem, chi, icpt)
         out[f"rbf.{tag}"] = host(o)
-        o = torch.full((n, rffs), 7.0, dtype=torch.float64, device=DEV)
-        g = torch.full((n, rffs, 1), 7.0, dtype=torch.float64, device=DEV)
+        o = alloc.out((n, rffs), torch.float64, fill=7.0, name=f"gradf.{tag}")
+        g = alloc.out((n, rffs, 1), torch.float64, fill=7.0, name=f"gradg.{tag}")
         ext.hipRBFGrad(x, o, g, radem, chi, SIGMA, icpt)
         out[f"gradf.{tag}"], out[f"gradg.{tag}"] = host(o), host(g)[:, :, 0]
-    x, chi = dev(case.x), dev(case.chi)
-    rows = torch.full((n, rffs), float("nan"), dtype=torch.float32, device=DEV)
+    x, chi = inp(case.x, "x"), inp(case.chi, "chi")
+    rows = alloc.out((n, rffs), torch.float32, fill=float("nan"), name="cache")
     ext.hipRBFFeatureCache(x, rows, radem, chi)
     out["cache"] = host(rows)
-    zr = torch.full((n, rffs), float("nan"), dtype=torch.float32, device=DEV)
-    gr = torch.full((n, rffs), float("nan"), dtype=torch.float32, device=DEV)
+    zr = alloc.out((n, rffs), torch.float32, fill=float("nan"), name="zrows")
+    gr = alloc.out((n, rffs), torch.float32, fill=float("nan"), name="grows")
     ext.hipRBFGradRows(x, zr, gr, radem, chi, SIGMA, icpt)
     out["zrows"], out["grows"] = host(zr), host(gr)
     if case.P <= 4096:
         rng = np.random.default_rng(rffs)
         v, y = rng.standard_normal(rffs), rng.standard_normal(n)
-        w = torch.full((rffs,), 7.0, dtype=torch.float64, device=DEV)
-        ext.hipZtZMatvec(x, radem, chi, dev(v), w, icpt)
-        zty = torch.full((rffs,), 7.0, dtype=torch.float64, device=DEV)
-        ext.hipZtY(x, radem, chi, dev(y), zty, icpt)
+        need = ext.ztz_workspace_bytes(rffs, radem.shape[2])
+        w = alloc.out((rffs,), torch.float64, fill=7.0, name="ztz")
+        ext.hipZtZMatvec(x, radem, chi, inp(v, "v"), w, icpt, alloc.workspace(need, name="ztz workspace"))
+        zty = alloc.out((rffs,), torch.float64, fill=7.0, name="zty")
+        ext.hipZtY(x, radem, chi, inp(y, "y"), zty, icpt, alloc.workspace(need, name="zty workspace"))
         out["ztz"], out["zty"], out["v"], out["y"] = host(w), host(zty), v, y
     return out
 
 
-def run_seq(ext, case, icpt):
-    n, rffs, cw, radem, out = case.n, case.rffs, case.cw, dev(case.radem), {}
+def run_seq(ext, case, icpt, alloc=None, sc=SC):
+    alloc = alloc or Plain(DEV)
+    inp = lambda a, name: alloc.inp(torch.from_numpy(np.ascontiguousarray(a)), name=name)
+    n, rffs, cw, radem, out = case.n, case.rffs, case.cw, inp(case.radem, "radem"), {}
     for dtype in BOTH:
-        x, chi, chi_all = (dev(a) for a in case.typed(dtype))
+        x, chi, chi_all = (inp(a, nm) for a, nm in zip(case.typed(dtype), ("x", "chi", "chi_all")))
         tag = np.dtype(dtype).name
-        o = torch.zeros((n, rffs), dtype=torch.float64, device=DEV)
-        ext.hipConv1dFGen(x, o, radem, chi, case.seqlen, cw, SC)
+        o = alloc.out((n, rffs), torch.float64, fill=0.0, name=f"conv.{tag}")
+        ext.hipConv1dFGen(x, o, radem, chi, case.seqlen, cw, sc)
         out[f"conv.{tag}"] = host(o)
-        o = torch.zeros((n, rffs), dtype=torch.float64, device=DEV)
-        g = torch.zeros((n, rffs, 1), dtype=torch.float64, device=DEV)
-        ext.hipConvGrad(x, o, radem, chi, case.seqlen, g, SIGMA, cw, SC)
+        o = alloc.out((n, rffs), torch.float64, fill=0.0, name=f"gradf.{tag}")
+        g = alloc.out((n, rffs, 1), torch.float64, fill=0.0, name=f"gradg.{tag}")
+        ext.hipConvGrad(x, o, radem, chi, case.seqlen, g, SIGMA, cw, sc)
         out[f"gradf.{tag}"], out[f"gradg.{tag}"] = host(o), host(g)[:, :, 0]
-        mp = torch.zeros((n, case.M), dtype=torch.float32, device=DEV)
+        mp = alloc.out((n, case.M), torch.float32, fill=0.0, name=f"maxpool.{tag}")
         ext.hipConv1dMaxpool(x, mp, radem, chi_all, case.seqlen, cw)
         out[f"maxpool.{tag}"] = host(mp)
-    x, chi = dev(case.x), dev(case.chi)
-    rows = torch.full((n, rffs), float("nan"), dtype=torch.float32, device=DEV)
-    ext.hipConvFeatureRows(x, rows, radem, chi, case.seqlen, cw, SC, icpt)
+    x, chi = inp(case.x, "x"), inp(case.chi, "chi")
+    rows = alloc.out((n, rffs), torch.float32, fill=float("nan"), name="rows")
+    ext.hipConvFeatureRows(x, rows, radem, chi, case.seqlen, cw, sc, icpt)
     out["rows"] = host(rows)
-    zr = torch.full((n, rffs), float("nan"), dtype=torch.float32, device=DEV)
-    gr = torch.full((n, rffs), float("nan"), dtype=torch.float32, device=DEV)
-    ext.hipConvGradRows(x, zr, gr, radem, chi, case.seqlen, SIGMA, cw, SC, icpt)
+    zr = alloc.out((n, rffs), torch.float32, fill=float("nan"), name="zrows")
+    gr = alloc.out((n, rffs), torch.float32, fill=float("nan"), name="grows")
+    ext.hipConvGradRows(x, zr, gr, radem, chi, case.seqlen, SIGMA, cw, sc, icpt)
     out["zrows"], out["grows"] = host(zr), host(gr)
     return out
+
+
+def run_guarded(run, ext, monkeypatch, case, icpt):
+    """``run`` with every array inside a guarded arena and exact internal workspaces; the arena verified before the values are used."""
+    arena = Arena(DEV)
+    with monkeypatch.context() as mp:
+        patched_workspaces(mp, ext, arena)
+        got = run(ext, case, icpt, arena)
+        arena.verify()
+    return got
 
 
 # ---------------------------------------------------------------------------------------------- ... against the dense reference
@@ -174,16 +191,16 @@ def check_seq(oracle, case, icpt, got):
 
 @pytest.mark.parametrize("icpt", [False, True])
 @pytest.mark.parametrize("n,d,rffs", DISPATCH_FIXED)
-def test_fixed_vector_arms(ext, oracle, n, d, rffs, icpt):
+def test_fixed_vector_arms(ext, oracle, monkeypatch, n, d, rffs, icpt):
     case = fixed_case(n, d, rffs, GRAD_SCALE)
-    check_fixed(oracle, case, icpt, run_fixed(ext, case, icpt))
+    check_fixed(oracle, case, icpt, run_guarded(run_fixed, ext, monkeypatch, case, icpt))
 
 
 @pytest.mark.parametrize("icpt", [False, True])
 @pytest.mark.parametrize("n,L,C,cw,rffs", DISPATCH_SEQ)
-def test_sequence_arms(ext, oracle, n, L, C, cw, rffs, icpt):
+def test_sequence_arms(ext, oracle, monkeypatch, n, L, C, cw, rffs, icpt):
     case = seq_case(n, L, C, cw, rffs, DISPATCH_SEQLEN)
-    check_seq(oracle, case, icpt, run_seq(ext, case, icpt))
+    check_seq(oracle, case, icpt, run_guarded(run_seq, ext, monkeypatch, case, icpt))
 
 
 # ---------------------------------------------------------------------------------------------- arms behind an environment switch
