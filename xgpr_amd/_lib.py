@@ -92,6 +92,10 @@ SIZE_FUNCS = {
     "xgpr_ztz_gram_workspace_bytes": [_l, _l],
     "xgpr_cross_gram_workspace_bytes": [_l, _l],
 }
+# ... and include/xgpr_hip_pool.h, the second public header (tests/test_pool_header_host.py checks it the same way)
+POOL_SIGNATURES = {
+    "xgpr_conv_token_maxpool_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _l, _l, _l, _l, _l, _l, _l, _l, _l, _i, _vp, _sz, _vp],
+}
 STRING_FUNCS = ["xgpr_last_error", "xgpr_build_arch", "xgpr_build_id"]
 
 _lib = None
@@ -110,7 +114,7 @@ def load():
             f"{LIB_PATH} is missing: the HIP extension has not been built "
             "(run `python xgpr_amd/build.py`); xgpr_amd has no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
-    for name, args in SIGNATURES.items():
+    for name, args in list(SIGNATURES.items()) + list(POOL_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = C.c_int

@@ -592,6 +592,46 @@ int conv_token_impl(const uint8_t *tokens, const float *table, float *zrows, flo
     });
 }
 
+// ---- token input for the max-pool operator (xgpr_conv_token_maxpool_f32): xgpr_conv1d_maxpool_f32 on table[tokens], bit for bit.  Its
+// checks are conv_impl's for MODE_MAXPOOL (one feature per frequency, radem_shape2 == reps * P) and conv_token_impl's for the table.
+int conv_token_maxpool_impl(const uint8_t *tokens, const float *table, float *out, const int8_t *radem, const float *chi,
+                            const int32_t *seqlen_host, const int32_t *seqlen_dev, long n, long L, long vocab, long C, long out_rows,
+                            long num_rffs, long num_freqs, long R, long nseq, int conv_width, void *workspace, size_t wbytes,
+                            void *stream) {
+    if (vocab < 1 || vocab > 256) return fail(XGPR_ERR_ARRAY_DIMS, "token table: vocab must be 1 .. 256 (uint8 tokens)");
+    if (C < 1) return fail(XGPR_ERR_ARRAY_DIMS, "token table: needs at least one column");
+    if (out_rows != n) return fail(XGPR_ERR_NO_DATAPOINTS, "no datapoints");
+    const long win = (long)conv_width * C;
+    const long P = padded_width(win > 0 ? win : 1);
+    const int reps = (int)((num_freqs + P - 1) / P);
+    int rc = check_sorf_shape(n, num_rffs, num_freqs, R, P, 1, [&] {
+        if (nseq != n) return fail(XGPR_ERR_SEQLEN_SIZE, "wrong array sizes");
+        if (L < conv_width || conv_width <= 0) return fail(XGPR_ERR_CONV_WIDTH, "invalid conv_width");
+        return 0;
+    });
+    if (rc) return rc;
+    if (R != (long)reps * P) return fail(XGPR_ERR_RFFS_FREQS, "incorrect number of rffs and or freqs.");
+    rc = check_seqlens(seqlen_host, nseq, n, L, conv_width);
+    if (rc) return rc;
+    if (!seqlen_dev) return fail(XGPR_ERR_WORKSPACE, "seqlen_dev (device copy of the sequence lengths) is required");
+    if (!tokens || !table || !out) return fail(XGPR_ERR_WORKSPACE, "tokens, table and out are required");
+    if (!conv_token_rows_ok(win, vocab, C))
+        return fail(XGPR_ERR_UNSUPPORTED, "token input serves windows of up to 1024 elements and tables of up to 4608 floats (see xgpr_conv_token_rows_ok)");
+    if (!workspace || wbytes < masks_bytes(R)) return fail(XGPR_ERR_WORKSPACE, "workspace too small (see xgpr_conv_workspace_bytes)");
+    hipStream_t st = (hipStream_t)stream;
+    WaveArgs a = wave_args(table, chi, workspace, n, L, win, num_freqs, R);
+    a.tokens = tokens; a.vocab = (int)vocab;
+    a.outf = out; a.seqlen = seqlen_dev; a.kmer_stride = (int)C; a.conv_width = conv_width;
+    a.scale = sqrt(1.0 / (double)num_freqs);
+    const int lg = ilog2(P);
+    return launch_wave_conv(a, radem, R, L, workspace, wbytes, st, [&](const WaveArgs &wa, long nblocks) {
+        return dispatch_lg<1, 10>(lg, TOO_WIDE_WAVE, [&](auto LG) {
+            return launch(wave_conv_tok_kernel<decltype(LG)::value, CONV_MAXPOOL>, dim3((unsigned)nblocks), dim3(256), 0, st,
+                          "wave_conv_tok_kernel launch", wa);
+        });
+    });
+}
+
 constexpr long ZTZ_MAX_SLABS = 2048;
 constexpr long ZTZ_ROW_WINDOW = 131072;    // two-pass matvec: rows per (dot, update) launch pair
 

@@ -444,9 +444,9 @@ __global__ __launch_bounds__(256, conv_min_blocks(LOG2P, MODE)) void wave_conv_k
     wave_conv_body<LOG2P, MODE>(a, win);
 }
 
-// the token forms (xgpr_conv_token_rows_f32 / xgpr_conv_token_grad_rows_f32: MODE CONV_ROWS / CONV_GRAD_ROWS).  a.x is the table [vocab,
-// kmer_stride] -- sigma-scaled for the feature rows, unscaled for the gradient rows, as x is --, a.tokens the uint8 [n, row_stride]
-// array, a.d = conv_width * kmer_stride.  The workgroup copies the table into LDS once, with one 0.0f behind it, before any wave leaves.
+// the token forms (xgpr_conv_token_rows_f32 / xgpr_conv_token_grad_rows_f32 / xgpr_conv_token_maxpool_f32: MODE CONV_ROWS /
+// CONV_GRAD_ROWS / CONV_MAXPOOL).  a.x is the table [vocab, kmer_stride] -- sigma-scaled for the feature rows, unscaled for the gradient
+// rows and the max-pool, as x is --, a.tokens the uint8 [n, row_stride] array, a.d = conv_width * kmer_stride.  The workgroup copies the table into LDS once, with one 0.0f behind it, before any wave leaves.
 // Windows of 512 / 1024 elements: the dense feature rows sit exactly at the 168 registers of three waves per SIMD, and the token form
 // holds 8 / 16 index registers more through the loop -- bound to three waves it spills 6 / 30 registers to scratch; it is built for two.
 constexpr int conv_tok_min_blocks(int LOG2P, int MODE) {
@@ -455,7 +455,8 @@ constexpr int conv_tok_min_blocks(int LOG2P, int MODE) {
 
 template <int LOG2P, int MODE>
 __global__ __launch_bounds__(256, conv_tok_min_blocks(LOG2P, MODE)) void wave_conv_tok_kernel(WaveArgs a) {
-    static_assert(MODE == CONV_ROWS || MODE == CONV_GRAD_ROWS, "token input serves the float32 row writers");
+    static_assert(MODE == CONV_ROWS || MODE == CONV_GRAD_ROWS || MODE == CONV_MAXPOOL,
+                  "token input serves the float32 row writers and the max-pool operator");
     __shared__ __attribute__((aligned(16))) float tab[TOK_TABLE_FLOATS + 4];
     const int nt = a.vocab * a.kmer_stride;             // <= TOK_TABLE_FLOATS (conv_token_rows_ok)
     for (int t = threadIdx.x; t < nt; t += 256) tab[t] = a.x[t];

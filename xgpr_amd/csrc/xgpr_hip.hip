@@ -45,6 +45,7 @@ typedef enum { ncclFloat64 = 8 } ncclDataType_t;
 #endif
 
 #include "../../include/xgpr_hip.h"
+#include "../../include/xgpr_hip_pool.h"
 
 namespace {
 
@@ -231,6 +232,13 @@ int xgpr_conv1d_maxpool_f32(const float *x, float *out, const int8_t *radem, con
     return conv_impl<float>(x, nullptr, nullptr, out, radem, chi, seqlen_host, seqlen_dev, n, L, C, out_rows, num_rffs,
                             0, 0, num_freqs, radem_shape2, nseq, 0.0, conv_width, 0, MODE_MAXPOOL, workspace,
                             workspace_bytes, stream);
+}
+int xgpr_conv_token_maxpool_f32(const uint8_t *tokens, const float *table, float *out, const int8_t *radem, const float *chi,
+                                const int32_t *seqlen_host, const int32_t *seqlen_dev, long n, long L, long vocab, long C,
+                                long out_rows, long num_rffs, long num_freqs, long radem_shape2, long nseq, int conv_width,
+                                void *workspace, size_t workspace_bytes, void *stream) {
+    return conv_token_maxpool_impl(tokens, table, out, radem, chi, seqlen_host, seqlen_dev, n, L, vocab, C, out_rows, num_rffs,
+                                   num_freqs, radem_shape2, nseq, conv_width, workspace, workspace_bytes, stream);
 }
 int xgpr_conv1d_maxpool_f64(const double *x, float *out, const int8_t *radem, const double *chi,
                             const int32_t *seqlen_host, const int32_t *seqlen_dev, long n, long L, long C,

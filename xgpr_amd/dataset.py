@@ -164,6 +164,25 @@ class DeviceDataset:
         """Host int32 sequence lengths of the shard, or None."""
         return self._sequence_lengths
 
+    def pooled(self, kernel):
+        """The dataset of the two-layer kernel's second layer: the same rows with x replaced by the resident pooled first
+        layer ``kernel.pool(x, sequence_lengths)``, float32 [n_local, init_rffs] -- computed once per kernel object (the
+        first layer depends on no hyperparameter) and returned again on every later call, whatever the hyperparameters.
+        y, its statistics, the global row count, ``comm``, the chunk size and the class count are this dataset's; it has no
+        sequence lengths, and its own ``scaled_x`` / ``feature_cache`` / ``feature_cache_f16`` are those of any
+        fixed-vector shard.  An empty local shard pools nothing."""
+        cached = getattr(self, "_pooled", None)
+        if cached is None or cached[0] is not kernel:
+            n = self._xdata.shape[0]
+            if n > 0:
+                xp = kernel.pool(self._xdata, self._sequence_lengths)
+            else:
+                xp = torch.zeros((0, kernel.init_rffs), dtype=torch.float32, device=kernel.device)
+            ds = DeviceDataset(xp, self._ydata, None, self._chunk_size, self._trainy_mean, self._trainy_std,
+                               self._ndatapoints, self.device, self.comm, self._max_class)
+            self._pooled = (kernel, ds)             # (the kernel object itself: an id alone could be reused after it dies)
+        return self._pooled[1]
+
     def feature_cache(self, kernel):
         """float32 feature cache of the whole shard for ``kernel`` at its current sigma (rebuilt when
         the kernel object or sigma changes)."""

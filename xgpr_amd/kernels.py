@@ -637,7 +637,22 @@ class Conv1dTwoLayerKernel(KernelBase):
     def fused_ok(self):
         return False
 
-    def _first_layer(self, input_x, sequence_length):
+    def _pool_into(self, input_x, slen, out):
+        """out [n, init_rffs] float32 (zero-filled by the caller: that is the ReLU) <- the max-pooled filters of ``input_x``:
+        a float32 [n, L, C] device tensor, or a TokenBatch on the device -- read as it is where the token operator serves its
+        shape (same bits as the dense array), otherwise expanded at most ``CACHE_BUILD_ROWS`` sequences at a time."""
+        if not isinstance(input_x, TokenBatch):
+            ext.hipConv1dMaxpool(input_x, out, self.radem_diag1, self.chi_arr1, slen, self.conv_width)
+        elif (torch.device(self.device).type == "cuda" and input_x.is_cuda and input_x.tokens.is_contiguous()
+              and ext.conv_token_rows_ok(self.conv_width * input_x.shape[2], input_x.table.shape[0], input_x.shape[2]) == 1):
+            ext.hipConvTokenMaxpool(input_x.tokens, input_x.table, out, self.radem_diag1, self.chi_arr1, slen, self.conv_width)
+        else:
+            for lo in range(0, input_x.shape[0], ConvSORFKernel.CACHE_BUILD_ROWS):
+                hi = min(lo + ConvSORFKernel.CACHE_BUILD_ROWS, input_x.shape[0])
+                ext.hipConv1dMaxpool(input_x[lo:hi].dense().contiguous(), out[lo:hi], self.radem_diag1, self.chi_arr1,
+                                     slen[lo:hi], self.conv_width)
+
+    def _first_layer(self, input_x, sequence_length, out=None):
         if sequence_length is None:
             raise ValueError("sequence_length is required for convolution kernels.")
         if input_x.shape[2] != self._xdim[2]:
@@ -645,19 +660,66 @@ class Conv1dTwoLayerKernel(KernelBase):
         if isinstance(sequence_length, torch.Tensor):
             sequence_length = sequence_length.cpu().numpy()
         slen = np.ascontiguousarray(sequence_length.astype(np.int32, copy=False))
-        featurized_x = torch.zeros((input_x.shape[0], self.init_rffs), dtype=torch.float32, device=self.device)
-        ext.hipConv1dMaxpool(input_x, featurized_x, self.radem_diag1, self.chi_arr1, slen, self.conv_width)
-        return featurized_x
+        if out is None:
+            out = torch.zeros((input_x.shape[0], self.init_rffs), dtype=torch.float32, device=self.device)
+        self._pool_into(input_x, slen, out)
+        return out
+
+    def _private_f32(self, input_x):
+        """The private float32 copy of a chunk on the device (kernel_baseclass.py:274-288); a TokenBatch moves to the device
+        as it is -- the first layer reads tokens."""
+        if isinstance(input_x, TokenBatch):
+            return input_x.to(self.device)
+        return self._as_device_f32(input_x).to(torch.float32, copy=True).contiguous()
+
+    POOL_SLICE_ROWS = 65536          # sequences per call when a whole shard is pooled: a float64 or non-contiguous input is
+                                     # converted slice by slice, never as a second shard-sized temporary
+
+    def pool(self, input_x, sequence_length):
+        """float32 [n, init_rffs]: the first layer of the kernel, max-pooled ReLU'd random convolution filters
+        (l2_conv1d.py:150-185 before sigma is applied).  It depends on no hyperparameter, so a dataset can keep it
+        (``DeviceDataset.pooled``).  ``input_x``: [n, L, C] floats (array or tensor, any device) or a TokenBatch; both are
+        pooled in slices of ``POOL_SLICE_ROWS`` sequences."""
+        if sequence_length is None:
+            raise ValueError("sequence_length is required for convolution kernels.")
+        if isinstance(input_x, np.ndarray):
+            input_x = torch.from_numpy(input_x)
+        n = input_x.shape[0]
+        out = torch.zeros((n, self.init_rffs), dtype=torch.float32, device=self.device)
+        for lo in range(0, n, self.POOL_SLICE_ROWS):
+            hi = min(lo + self.POOL_SLICE_ROWS, n)
+            xin = input_x[lo:hi]
+            xin = xin.to(self.device) if isinstance(xin, TokenBatch) else xin.to(self.device, torch.float32).contiguous()
+            self._first_layer(xin, sequence_length[lo:hi], out[lo:hi])
+        return out
+
+    def second_layer(self):
+        """The second layer as a fixed-vector kernel over the pooled features: an RBF ``SORFKernel`` of xdim (n, init_rffs)
+        whose ``transform_x`` / ``gradient_x`` of ``pool(x, sl)`` are this kernel's of (x, sl), bit for bit -- both end in the
+        same operator call on the same sigma-scaled rows.  One view per kernel object (the dataset caches key on the kernel
+        object); it shares the draws (the same tensors), the intercept flag, the feature count, the device and the
+        hyperparameters, which either object may set."""
+        if getattr(self, "_second", None) is None:
+            self._second = _SecondLayerView(self)
+        return self._second
 
     def transform_x(self, input_x, sequence_length=None):
         """kernel_baseclass.py:269-299 with l2_conv1d.py:150-185."""
-        xin = self._as_device_f32(input_x).to(torch.float32, copy=True).contiguous()
+        xin = self._private_f32(input_x)
         featurized_x = scale_input(self._first_layer(xin, sequence_length), self.hyperparams[1])
         xtrans = torch.zeros((featurized_x.shape[0], self.num_rffs), dtype=torch.float64, device=self.device)
         ext.hipRBFFeatureGen(featurized_x, xtrans, self.radem_diag, self.chi_arr, self.fit_intercept)
         if self.fit_intercept:
             xtrans[:, 0] = 1.
         return xtrans
+
+    def gradient_x(self, input_x, sequence_length=None):
+        """kernel_baseclass.py:328-361; token input goes to the first layer as it is."""
+        xtrans, xgrad = self.kernel_specific_gradient(self._private_f32(input_x), sequence_length)
+        if self.fit_intercept:
+            xtrans[:, 0] = 1.
+            xgrad[:, 0, :] = 0.
+        return xtrans, xgrad
 
     def kernel_specific_gradient(self, input_x, sequence_length=None):
         """l2_conv1d.py:189-222."""
@@ -676,9 +738,8 @@ class Conv1dTwoLayerKernel(KernelBase):
 
     def fill_grad_rows(self, x_unscaled, zrows, grows, sequence_length):
         """zrows, grows [w, M] float32 <- ``gradient_x`` of the UNSCALED float32 sequences, exactly: the gradient is
-        hipRBFGrad over the max-pooled float32 first-layer features, every entry of which is a float32 value."""
-        if isinstance(x_unscaled, TokenBatch):
-            x_unscaled = x_unscaled.dense()
+        hipRBFGrad over the max-pooled float32 first-layer features, every entry of which is a float32 value.  A TokenBatch
+        is pooled from its tokens (``_pool_into``)."""
         ext.hipRBFGradRows(self._first_layer(x_unscaled, sequence_length), zrows, grows, self.radem_diag, self.chi_arr,
                            float(self.hyperparams[1]), self.fit_intercept)
 
@@ -696,6 +757,39 @@ class Conv1dTwoLayerKernel(KernelBase):
     ztz_block_cached = ConvSORFKernel.ztz_block_cached
     cache_rows_to_features = ConvSORFKernel.cache_rows_to_features
     workspace_bytes = ConvSORFKernel.workspace_bytes
+
+
+class _SecondLayerView(SORFKernel):
+    """``Conv1dTwoLayerKernel.second_layer()``: the RBF layer of a two-layer kernel as a ``SORFKernel`` over the pooled
+    features.  Nothing is drawn: ``radem_diag`` and ``chi_arr`` ARE the owner's second-layer tensors, and ``hyperparams`` is
+    the owner's attribute, read and written through -- the tuning routines set hyperparameters on the kernel they are
+    handed, and both objects must see them."""
+
+    def __init__(self, owner):
+        KernelBase.__init__(self, owner.num_rffs, (owner._xdim[0], owner.init_rffs), owner.kernel_spec_parms, owner.device)
+        self.owner = owner
+        self.random_seed = owner.random_seed
+        self.kernel_choice = "RBF"
+        self.fit_intercept = owner.fit_intercept
+        self.radem_diag, self.chi_arr = owner.radem_diag, owner.chi_arr
+
+    @property
+    def hyperparams(self):
+        return self.owner.hyperparams
+
+    @hyperparams.setter
+    def hyperparams(self, value):
+        if getattr(self, "owner", None) is not None:      # (KernelBase.__init__ assigns its default before the owner is known)
+            self.owner.hyperparams = value
+
+    def sibling(self, num_rffs):
+        """The second layer of a two-layer kernel of the same family, seed, settings and hyperparameters with ``num_rffs``
+        features (preconditioner.check_rank_ratio samples kernels beyond 8192 features with an 8192-feature one): its first
+        layer draws what the owner's drew, so it reads the same pooled dataset."""
+        twin = Conv1dTwoLayerKernel(self.owner._xdim, num_rffs, self.owner.random_seed, self.owner.device,
+                                    self.owner.kernel_spec_parms)
+        twin.set_hyperparams(self.owner.get_hyperparams(logspace=False), logspace=False)
+        return twin.second_layer()
 
 
 class MiniARDKernel(KernelBase):

@@ -21,7 +21,7 @@ from .dataset import TokenBatch, token_batch
 from .kernels import make_kernel
 from .preconditioner import RandNysPreconditioner, autoselect_preconditioner
 from .crude_tuning import tune_hyperparams_crude as _tune_crude
-from .tuning import tune_hyperparams as _tune
+from .tuning import default_bounds as _default_bounds, tune_hyperparams as _tune
 
 MAX_VARIANCE_RFFS = 4096            # constants.py:2
 MAX_CLOSED_FORM_RFFS = 8192         # constants.py:3
@@ -57,6 +57,20 @@ class _ModelBase:
         self.weights = self.var = self.gamma = None
         self.trainy_mean, self.trainy_std = 0.0, 1.0
 
+    # The two-layer kernel's solver passes run on its second layer over the dataset's resident pooled first layer
+    # (Conv1dTwoLayerKernel.second_layer / DeviceDataset.pooled): a fixed-vector RBF problem.  False keeps every pass on the
+    # two-layer kernel and the original dataset.
+    pool_first_layer = True
+
+    def _solver_pair(self, dataset):
+        """-> (kernel, dataset) the solver passes are handed.  The weights live in the same feature space either way."""
+        kernel = self.kernel
+        if (self.pool_first_layer and getattr(kernel, "kernel_choice", None) == "Conv1dTwoLayer"
+                and hasattr(kernel, "second_layer") and torch.device(kernel.device).type == "cuda"
+                and hasattr(dataset, "pooled")):
+            return kernel.second_layer(), dataset.pooled(kernel)
+        return kernel, dataset
+
     def _initialize_kernel(self, dataset):
         if self.kernel is None:
             self.kernel = make_kernel(self.kernel_choice, dataset.get_xdim(), self.num_rffs, self.random_seed,
@@ -85,7 +99,8 @@ class _ModelBase:
             raise RuntimeError("Invalid value for max_rank.")
         if max_rank >= self.kernel.get_num_rffs():
             raise RuntimeError("Max rank should be < the number of rffs.")
-        pre = RandNysPreconditioner(self.kernel, dataset, max_rank, self.verbose, self.random_seed, method,
+        kernel, dataset = self._solver_pair(dataset)
+        pre = RandNysPreconditioner(kernel, dataset, max_rank, self.verbose, self.random_seed, method,
                                     is_regression=self.is_regression)
         return pre, pre.achieved_ratio
 
@@ -103,22 +118,23 @@ class xGPRegression(_ModelBase):
         self._initialize_kernel(dataset)
         self.trainy_mean, self.trainy_std = dataset.get_ymean(), dataset.get_ystd()
         self.weights = self.var = None
+        kernel, dataset = self._solver_pair(dataset)
         if mode == "exact":
-            if self.kernel.get_num_rffs() > MAX_CLOSED_FORM_RFFS:
+            if kernel.get_num_rffs() > MAX_CLOSED_FORM_RFFS:
                 raise RuntimeError(f"You specified 'exact' fitting, but the number of rffs is > {MAX_CLOSED_FORM_RFFS}.")
-            self.weights, n_iter, losses = calc_weights_exact(dataset, self.kernel)
+            self.weights, n_iter, losses = calc_weights_exact(dataset, kernel)
         elif mode == "cg":
             if preconditioner is None:
                 preconditioner, _, _ = autoselect_preconditioner(
-                    self.kernel, dataset, min_rank, max_rank, 512, always_use_srht2, autoselect_target_ratio,
+                    kernel, dataset, min_rank, max_rank, 512, always_use_srht2, autoselect_target_ratio,
                     self.random_seed, True, self.verbose)
-            self.weights, n_iter, losses = cg_fit_lib_internal(self.kernel, dataset, tol, max_iter, preconditioner,
+            self.weights, n_iter, losses = cg_fit_lib_internal(kernel, dataset, tol, max_iter, preconditioner,
                                                                self.verbose, cache_features=cache_features)
         else:
             raise RuntimeError("Unrecognized fitting mode supplied. Must provide one of 'cg', 'exact'.")
         if not suppress_var:
-            nvar = min(self.variance_rffs, self.kernel.get_num_rffs())
-            self.var = calc_variance_exact(self.kernel, dataset, nvar)
+            nvar = min(self.variance_rffs, kernel.get_num_rffs())
+            self.var = calc_variance_exact(kernel, dataset, nvar)
         if run_diagnostics:
             return n_iter, losses
 
@@ -155,29 +171,32 @@ class xGPRegression(_ModelBase):
 
     def exact_nmll(self, hyperparams, dataset):
         self.set_hyperparams(hyperparams, dataset)
-        return _nmll.exact_nmll(self.kernel, dataset)
+        return _nmll.exact_nmll(*self._solver_pair(dataset))
 
     def exact_nmll_gradient(self, hyperparams, dataset, subsample=1):
         self.set_hyperparams(hyperparams, dataset)
-        return _nmll.exact_nmll_gradient(self.kernel, dataset, subsample)
+        return _nmll.exact_nmll_gradient(*self._solver_pair(dataset), subsample)
 
     def approximate_nmll(self, hyperparams, dataset, manual_settings=None):
         self.set_hyperparams(hyperparams, dataset)
-        return _nmll.approximate_nmll(self.kernel, dataset, None, manual_settings, self.random_seed)
+        return _nmll.approximate_nmll(*self._solver_pair(dataset), None, manual_settings, self.random_seed)
 
     def tune_hyperparams(self, dataset, bounds=None, max_iter=50, tuning_method="Powell", starting_hyperparams=None,
                          tol=1e-2, n_restarts=1, nmll_method="exact", manual_settings=None):
         self._initialize_kernel(dataset)
         self.weights = self.var = None
-        return _tune(self.kernel, dataset, bounds, max_iter, tuning_method, starting_hyperparams, tol, n_restarts,
+        if bounds is None:                   # the two-layer kernel's own bounds, whichever object the routine is handed
+            bounds = _default_bounds(self.kernel)
+        return _tune(*self._solver_pair(dataset), bounds, max_iter, tuning_method, starting_hyperparams, tol, n_restarts,
                      nmll_method, manual_settings, self.random_seed, self.verbose)
-
 
     def tune_hyperparams_crude(self, dataset, bounds=None, random_seed=123, max_bayes_iter=30, subsample=1):
         """xgp_regression.py:497-561."""
         self._initialize_kernel(dataset)
         self.weights = self.var = None
-        return _tune_crude(self.kernel, dataset, bounds, random_seed, max_bayes_iter, subsample, self.verbose)
+        if bounds is None:
+            bounds = _default_bounds(self.kernel)
+        return _tune_crude(*self._solver_pair(dataset), bounds, random_seed, max_bayes_iter, subsample, self.verbose)
 
 
 class xGPClassification(_ModelBase):
@@ -192,11 +211,12 @@ class xGPClassification(_ModelBase):
         """xgp_classification.py:111-200."""
         refuse_half_cache(cache_features, "xGPClassification.fit")
         self._initialize_kernel(dataset)
+        kernel, dataset = self._solver_pair(dataset)
         if preconditioner is None:
             preconditioner, _, _ = autoselect_preconditioner(
-                self.kernel, dataset, min_rank, max_rank, 512, always_use_srht2, autoselect_target_ratio,
+                kernel, dataset, min_rank, max_rank, 512, always_use_srht2, autoselect_target_ratio,
                 self.random_seed, False, self.verbose)
-        self.weights, self.gamma, n_iter, losses = fit_classifier(self.kernel, dataset, preconditioner, tol, max_iter,
+        self.weights, self.gamma, n_iter, losses = fit_classifier(kernel, dataset, preconditioner, tol, max_iter,
                                                                   self.verbose, cache_features)
         if run_diagnostics:
             return n_iter, losses
@@ -228,7 +248,8 @@ class KernelFGen:
         self.kernel.set_hyperparams(full, logspace=True)
 
     def predict(self, input_x, sequence_lengths=None, chunk_size=2000, token_table=None):
-        """-> numpy [N, num_rffs].  Token input (a TokenBatch, or integer tokens with ``token_table``) is expanded chunk by chunk."""
+        """-> numpy [N, num_rffs].  Token input (a TokenBatch, or integer tokens with ``token_table``) is expanded chunk by
+        chunk; the two-layer kernel pools it from the tokens (``Conv1dTwoLayerKernel.transform_x``)."""
         input_x = token_input(input_x, token_table, self.device)
         preds = []
         for i in range(0, input_x.shape[0], chunk_size):
@@ -254,9 +275,12 @@ class FastConv1d:
         self.radem_diag = torch.from_numpy(np.ascontiguousarray(radem)).to(device)
         self.chi_arr = torch.from_numpy(chi_arr).to(device)
 
-    def predict(self, x_array, sequence_lengths, chunk_size=2000):
-        """-> numpy float32 [N, num_features]"""
+    def predict(self, x_array, sequence_lengths, chunk_size=2000, token_table=None):
+        """-> numpy float32 [N, num_features].  ``x_array`` may be a TokenBatch, or with ``token_table`` an integer token
+        array [N, L]: pooled from the tokens (hipConvTokenMaxpool) where the token operator serves the shape, otherwise
+        expanded chunk by chunk."""
         from . import xgpr_hip_rfgen_ext as ext
+        x_array = token_input(x_array, token_table, self.device)
         if sequence_lengths.shape[0] != x_array.shape[0]:
             raise RuntimeError("The shape[0] of sequence_lengths must match the shape[0] of x_array.")
         if x_array.shape[2] != self.seq_width:
@@ -264,11 +288,18 @@ class FastConv1d:
         feats = []
         for i in range(0, x_array.shape[0], chunk_size):
             xin = x_array[i:i + chunk_size]
+            slen = np.ascontiguousarray(np.asarray(sequence_lengths[i:i + chunk_size]).astype(np.int32))
+            out = torch.zeros((xin.shape[0], self.num_features), dtype=torch.float32, device=self.device)
+            if isinstance(xin, TokenBatch):
+                xin = xin.to(self.device)
+                if ext.conv_token_rows_ok(self.conv_width * self.seq_width, xin.table.shape[0], self.seq_width) == 1:
+                    ext.hipConvTokenMaxpool(xin.tokens.contiguous(), xin.table.contiguous(), out, self.radem_diag, self.chi_arr,
+                                            slen, self.conv_width)
+                    feats.append(out)
+                    continue
+                xin = xin.dense()
             xin = torch.from_numpy(np.ascontiguousarray(xin)) if isinstance(xin, np.ndarray) else xin
             xin = xin.to(self.device, torch.float32).contiguous()
-            out = torch.zeros((xin.shape[0], self.num_features), dtype=torch.float32, device=self.device)
-            ext.hipConv1dMaxpool(xin, out, self.radem_diag, self.chi_arr,
-                                 np.ascontiguousarray(np.asarray(sequence_lengths[i:i + chunk_size]).astype(np.int32)),
-                                 self.conv_width)
+            ext.hipConv1dMaxpool(xin, out, self.radem_diag, self.chi_arr, slen, self.conv_width)
             feats.append(out)
         return torch.cat(feats).cpu().numpy()

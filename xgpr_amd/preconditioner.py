@@ -358,10 +358,13 @@ def check_rank_ratio(kernel, dataset, sample_frac=0.1, max_rank=512, random_seed
         raise RuntimeError("sample_frac must be in the range [0.01, 1]")
     check_kernel = kernel
     if kernel.get_num_rffs() > 8192:
-        from .kernels import make_kernel
-        check_kernel = make_kernel(kernel.kernel_choice, dataset.get_xdim(), 8192, kernel.random_seed, kernel.device,
-                                   kernel.kernel_spec_parms)
-        check_kernel.set_hyperparams(kernel.get_hyperparams(logspace=False), logspace=False)
+        if hasattr(kernel, "sibling"):       # the second layer of a two-layer kernel: the same layer of an 8192-feature twin
+            check_kernel = kernel.sibling(8192)
+        else:
+            from .kernels import make_kernel
+            check_kernel = make_kernel(kernel.kernel_choice, dataset.get_xdim(), 8192, kernel.random_seed, kernel.device,
+                                       kernel.kernel_spec_parms)
+            check_kernel.set_hyperparams(kernel.get_hyperparams(logspace=False), logspace=False)
     s_mat = srht_ratio_check(dataset, max_rank, check_kernel, random_seed, verbose, sample_frac)
     return float(s_mat.min().item() / kernel.get_lambda() ** 2) / sample_frac
 

@@ -546,6 +546,27 @@ def hipConv1dMaxpool(inputArr, outputArr, radem, chiArr, seqlengths, convWidth):
         radem.shape[2], host.shape[0], int(convWidth), wp, wn, _stream()))
 
 
+@_array_args("tokens", "table", "outputArr", "radem", "chiArr")
+def hipConvTokenMaxpool(tokens, table, outputArr, radem, chiArr, seqlengths, convWidth):
+    """hipConv1dMaxpool for sequences given as tokens (xgpr_conv_token_maxpool_f32): ``tokens`` [N, L] uint8 index the rows of
+    ``table`` [V, C] float32, and ``outputArr`` [N, num_rffs] float32 becomes max(outputArr, ...) over the k-mers, exactly as
+    hipConv1dMaxpool leaves it for the dense array ``table[tokens]`` (the caller zero-fills it).  Shapes for which
+    ``conv_token_rows_ok`` is 0 raise RuntimeError and launch nothing."""
+    t = _dev(tokens, "tokens", torch.uint8, 2)
+    tab = _dev(table, "table", torch.float32, 2)
+    o = _dev(outputArr, "outputArr", torch.float32, 2)
+    r = _radem3(radem)
+    c = _dev(chiArr, "chiArr", torch.float32, 1)
+    host, dev = _seqlens(seqlengths, tokens.device)
+    n = tokens.shape[0]
+    nbytes = _LIB.xgpr_conv_workspace_bytes(radem.shape[2], int(convWidth) * table.shape[1], 4, n)
+    ws, wp, wn = _workspace(nbytes, tokens.device)
+    return _lib.check(_LIB.xgpr_conv_token_maxpool_f32(
+        t, tab, o, r, c, C.c_void_p(host.ctypes.data), C.c_void_p(dev.data_ptr()), n, tokens.shape[1], table.shape[0],
+        table.shape[1], outputArr.shape[0], outputArr.shape[1], chiArr.shape[0], radem.shape[2], host.shape[0], int(convWidth),
+        wp, wn, _stream()))
+
+
 @_array_args("inputArr", "radem", "chiArr", "vec", "outVec", "workspace")
 def hipZtZMatvec(inputArr, radem, chiArr, vec, outVec, fitIntercept, workspace=None, masksPacked=False):
     """Fused ``Z.T @ (Z @ vec)`` over one shard of (sigma-scaled, float32) rows: the chunk
@@ -925,6 +946,7 @@ cudaConv1dFGen = hipConv1dFGen
 cudaConvGrad = hipConvGrad
 cudaConvTokenRows = hipConvTokenRows
 cudaConvTokenGradRows = hipConvTokenGradRows
+cudaConvTokenMaxpool = hipConvTokenMaxpool
 cudaRowsToHalf = hipRowsToHalf
 cudaZCacheMatvecHalf = hipZCacheMatvecHalf
 cudaZCacheMatvecHalfScaled = hipZCacheMatvecHalfScaled
