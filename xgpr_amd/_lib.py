@@ -96,6 +96,11 @@ SIZE_FUNCS = {
 POOL_SIGNATURES = {
     "xgpr_conv_token_maxpool_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _l, _l, _l, _l, _l, _l, _l, _l, _l, _i, _vp, _sz, _vp],
 }
+# ... and include/xgpr_hip_input_grad.h, the third (tests/test_input_grad_host.py)
+INPUT_GRAD_SIGNATURES = {
+    "xgpr_rbf_input_grad_ok": [_l, _l],
+    "xgpr_rbf_input_grad_f32": [_vp, _vp, _vp, _vp, _vp, _l, _l, _l, _l, _l, _l, _d, _i, _vp, _sz, _vp],
+}
 STRING_FUNCS = ["xgpr_last_error", "xgpr_build_arch", "xgpr_build_id"]
 
 _lib = None
@@ -114,7 +119,7 @@ def load():
             f"{LIB_PATH} is missing: the HIP extension has not been built "
             "(run `python xgpr_amd/build.py`); xgpr_amd has no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
-    for name, args in list(SIGNATURES.items()) + list(POOL_SIGNATURES.items()):
+    for name, args in list(SIGNATURES.items()) + list(POOL_SIGNATURES.items()) + list(INPUT_GRAD_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = C.c_int

@@ -46,6 +46,7 @@ typedef enum { ncclFloat64 = 8 } ncclDataType_t;
 
 #include "../../include/xgpr_hip.h"
 #include "../../include/xgpr_hip_pool.h"
+#include "../../include/xgpr_hip_input_grad.h"
 
 namespace {
 
@@ -64,6 +65,7 @@ namespace {
 #include "mini_ard.inc"
 #include "cg_kernels.inc"
 #include "launchers.inc"
+#include "input_grad.inc"
 
 }  // namespace
 
@@ -512,6 +514,15 @@ int xgpr_debug_zb_stamps(void *dst, size_t bytes) {
     return (int)(sizeof(g_zb_stamps) / 8);
 }
 #endif
+
+// ---- include/xgpr_hip_input_grad.h
+int xgpr_rbf_input_grad_ok(long d, long num_freqs) { return rbf_input_grad_ok_impl(d, num_freqs); }
+int xgpr_rbf_input_grad_f32(const float *x, const double *w, double *g, const int8_t *radem, const float *chi, long n, long d,
+                            long w_row_stride, long w_cols, long num_freqs, long radem_shape2, double sigma, int fit_intercept,
+                            void *workspace, size_t workspace_bytes, void *stream) {
+    return rbf_input_grad_impl(x, w, g, radem, chi, n, d, w_row_stride, w_cols, num_freqs, radem_shape2, sigma, fit_intercept,
+                               workspace, workspace_bytes, stream);
+}
 
 int xgpr_selftest_lane_xor(int32_t *out, void *stream) {
     hipLaunchKernelGGL(selftest_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, out);

@@ -268,6 +268,59 @@ class SORFKernel(KernelBase):
             z[:, 0] = 1.
         return z
 
+    # ---- derivative of a weighted sum of the features with respect to the INPUT: the transposed SORF
+    def _input_grad_weights(self, weights, w_cols, n):
+        w = weights if isinstance(weights, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(weights))
+        w = w.to(self.device, torch.float64)
+        if w.dim() not in (1, 2) or (w.dim() == 2 and w.shape[0] != n):
+            raise RuntimeError("weights must be one vector, or one row per datapoint.")
+        if w.dim() == 1 or w.stride(1) != 1:
+            w = w.contiguous()
+        w_cols = min(w.shape[-1], self.num_rffs) if w_cols is None else int(w_cols)
+        if w_cols < 2 or w_cols % 2 or w_cols > min(w.shape[-1], self.num_rffs):
+            raise RuntimeError("w_cols must be even, >= 2 and within the weights and the features.")
+        return w, w_cols
+
+    def input_gradient(self, input_x, weights, w_cols=None):
+        """float64 device tensor [n, d]: d/dx of ``transform_x(x) @ weights`` at every row of the UNSCALED ``input_x``.
+        ``weights`` float64, one vector [>= w_cols] for all rows or one row per datapoint [n, >= w_cols]; only the first
+        ``w_cols`` feature columns (even; default all the weights cover) carry weight.  With the intercept, column 0 of the
+        features is the constant 1 and ``weights[..., 0]`` does not enter.  One HIP kernel at padded width <= 1024
+        (``ext.rbf_input_grad_ok``); wider inputs are composed from the feature operator and three transforms."""
+        xs = self.scaled_f32(input_x)
+        w, w_cols = self._input_grad_weights(weights, w_cols, xs.shape[0])
+        if ext.rbf_input_grad_ok(xs.shape[1], self.num_freqs):
+            out = torch.empty(tuple(xs.shape), dtype=torch.float64, device=self.device)
+            ext.hipRBFInputGrad(xs, w, out, self.radem_diag, self.chi_arr, float(self.hyperparams[1]), self.fit_intercept,
+                                w_cols=w_cols)
+            return out
+        return self.input_gradient_composed(xs, w, w_cols)
+
+    def input_gradient_composed(self, x_scaled, weights, w_cols):
+        """The same gradient from existing device operators, at every width: float64 features with the intercept OFF (with
+        it on, column 0 no longer holds cos p_0) rescaled by the ratio of the two constants, chi (.) u zero-padded to whole
+        transforms, three rounds of { FHT ; signs x normaliser } in the order 2, 1, 0 as ``MiniARDKernel.precompute_weights``
+        applies them to the identity, the sum over the transforms and the product with sigma."""
+        n, d = x_scaled.shape
+        nf, p = self.num_freqs, padded_dims(d)
+        nblocks = self.radem_diag.shape[2] // p
+        z = torch.empty((n, self.num_rffs), dtype=torch.float64, device=self.device)
+        ext.hipRBFFeatureGen(x_scaled, z, self.radem_diag, self.chi_arr, False)
+        z *= self.row_cache_params()[1] / float(np.float32(np.sqrt(1.0 / nf)))
+        h = w_cols // 2
+        wc, ws = weights[..., 0:w_cols:2].clone(), weights[..., 1:w_cols:2]
+        if self.fit_intercept:
+            wc[..., 0] = 0.
+        t = torch.zeros((n, nblocks * p), dtype=torch.float64, device=self.device)
+        t[:, :h] = (ws * z[:, 0:w_cols:2] - wc * z[:, 1:w_cols:2]) * self.chi_arr[:h].to(torch.float64)
+        t = t.reshape(n * nblocks, p)
+        norm_constant = 1.0 / (2.0 ** (np.log2(p) / 2.0))
+        radem = self.radem_diag.to(torch.float64)
+        for r in (2, 1, 0):
+            ext.hipFastHadamardTransform2D(t)
+            t = (t.view(n, nblocks, p) * (radem[r, 0].view(1, nblocks, p) * norm_constant)).reshape(n * nblocks, p)
+        return (t.view(n, nblocks, p).sum(dim=1)[:, :d] * float(self.hyperparams[1])).contiguous()
+
     def fused_ok(self):
         """The fused kernels cover padded width <= 4096 (single pass up to num_freqs = 7168 -- 4096 at padded widths
         2048 / 4096, whose transforms span two / four wave tiles --, the two-pass form beyond, up to 65536)."""

@@ -928,6 +928,50 @@ def ztz_matvec_plan(d, num_freqs):
     return int(_LIB.xgpr_ztz_matvec_plan(int(d), int(num_freqs)))
 
 
+def rbf_input_grad_ok(d, num_freqs):
+    """Whether hipRBFInputGrad's kernel serves an input of ``d`` columns (padded width up to 1024); no device work."""
+    return int(_LIB.xgpr_rbf_input_grad_ok(int(d), int(num_freqs)))
+
+
+def hipRBFInputGrad(x_scaled, weights, out, radem, chi, sigma, fit_intercept, w_cols=None, workspace=None):
+    """``out[n, d]`` (float64, overwritten) <- d/dx of ``features(x) @ weights`` for the fixed-vector kernels, through the
+    transposed SORF (include/xgpr_hip_input_grad.h).  ``x_scaled`` [n, d] float32 is already multiplied by sigma, as for the
+    feature operators.  ``weights`` float64: 1-d, one vector for all rows, or 2-d [n, stride] with unit column stride, one
+    vector per row (what lies past ``w_cols`` in a row is never read).  Only the first ``w_cols`` feature columns carry
+    weight (even; default: all of them).  Under fit_intercept ``weights[..., 0]`` is ignored (column 0 is the constant 1)."""
+    x = _dev(x_scaled, "x_scaled", torch.float32, 2)
+    g = _dev(out, "out", torch.float64, 2)
+    r = _radem3(radem)
+    c = _dev(chi, "chi", torch.float32, 1)
+    n, d = x_scaled.shape
+    if tuple(out.shape) != (n, d):
+        raise RuntimeError("Wrong array sizes.")
+    if not isinstance(weights, torch.Tensor) or not weights.is_cuda or weights.dtype != torch.float64:
+        raise TypeError("weights: expected a float64 device tensor")
+    if weights.dim() == 1:
+        if not weights.is_contiguous():
+            raise TypeError("weights: expected a C-contiguous array")
+        stride, avail = 0, weights.shape[0]
+    elif weights.dim() == 2:
+        if weights.shape[0] != n:
+            raise RuntimeError("Wrong array sizes.")
+        if weights.stride(1) != 1 or (n > 1 and weights.stride(0) < weights.shape[1]):
+            raise TypeError("weights: expected rows of contiguous float64 values")
+        stride, avail = (weights.stride(0) if n > 1 else weights.shape[1]), weights.shape[1]
+    else:
+        raise TypeError("weights: expected 1 or 2 dims")
+    w_cols = 2 * chi.shape[0] if w_cols is None else int(w_cols)
+    if w_cols > avail:
+        raise RuntimeError("Wrong array sizes.")
+    if workspace is None:
+        ws, wp, wn = _workspace(_LIB.xgpr_rbf_workspace_bytes(radem.shape[2]), x_scaled.device)
+    else:
+        ws, wp, wn = workspace, C.c_void_p(workspace.data_ptr()), C.c_size_t(workspace.numel() * workspace.element_size())
+    return _lib.check(_LIB.xgpr_rbf_input_grad_f32(
+        x, C.c_void_p(weights.data_ptr()), g, r, c, n, d, stride, w_cols, chi.shape[0], radem.shape[2], float(sigma),
+        int(bool(fit_intercept)), wp, wn, _stream()))
+
+
 def selftest_lane_xor(device="cuda"):
     """Runs the cross-lane butterfly self test; returns an int32 [6, 16, 64] CPU array."""
     out = torch.zeros(6 * 16 * 64, dtype=torch.int32, device=device)
