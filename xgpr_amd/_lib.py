@@ -101,6 +101,14 @@ INPUT_GRAD_SIGNATURES = {
     "xgpr_rbf_input_grad_ok": [_l, _l],
     "xgpr_rbf_input_grad_f32": [_vp, _vp, _vp, _vp, _vp, _l, _l, _l, _l, _l, _l, _d, _i, _vp, _sz, _vp],
 }
+# ... and include/xgpr_hip_seq_input_grad.h, the fourth (tests/test_seq_input_grad_host.py)
+SEQ_INPUT_GRAD_SIGNATURES = {
+    "xgpr_conv_input_grad_ok": [_l, _l],
+    "xgpr_conv_token_input_grad_ok": [_l, _l, _l],
+    "xgpr_conv_input_grad_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _l, _l, _l, _l, _l, _l, _l, _d, _i, _i, _i, _vp, _sz, _vp],
+    "xgpr_conv_token_input_grad_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _l, _l, _l, _l, _l, _l, _l, _l, _d, _i, _i, _i, _vp,
+                                       _sz, _vp],
+}
 STRING_FUNCS = ["xgpr_last_error", "xgpr_build_arch", "xgpr_build_id"]
 
 _lib = None
@@ -119,7 +127,8 @@ def load():
             f"{LIB_PATH} is missing: the HIP extension has not been built "
             "(run `python xgpr_amd/build.py`); xgpr_amd has no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
-    for name, args in list(SIGNATURES.items()) + list(POOL_SIGNATURES.items()) + list(INPUT_GRAD_SIGNATURES.items()):
+    for name, args in (list(SIGNATURES.items()) + list(POOL_SIGNATURES.items()) + list(INPUT_GRAD_SIGNATURES.items())
+                       + list(SEQ_INPUT_GRAD_SIGNATURES.items())):
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = C.c_int

@@ -31,6 +31,57 @@ struct InputGradArgs {
     double sigma;
 };
 
+// One tile (1024 frequencies, tile b) of the gradient, shared by the fixed-vector kernel below and the sequence kernel
+// (seq_input_grad.inc).  On entry v holds the sigma-scaled row -- or k-mer window -- replicated over the tile's 1024 / P transforms
+// (wave_load's layout C); on return it holds the tile's part of W^T u in layout C, every repetition on its own.  `scale` is the
+// feature constant of u (the sequence kernels divide it by the k-mer normaliser), `chs` chi's factor with the sign tile_sorf kept.
+template <int LOG2P>
+__device__ __forceinline__ void input_grad_tile(float (&v)[16], const InputGradArgs &a, const double *wrow, double scale, int b, float chs,
+                                                float *tb, int lane) {
+    constexpr bool TP = LOG2P >= 7;
+    const long hcols = a.w_cols >> 1;                    // frequencies with a weight pair
+    const cmask_t mk = as_cmask(a.masks + (long)b * 16);
+    // ---- forward: the feature operators' front end (the tile is loaded by the caller)
+    uint32_t sw[3] = {0, 0, 0};
+    if constexpr (TP) load_sign_words(sw, a.masks, a.MW, b, lane);
+    tile_sorf<LOG2P, TP, TP, false>(v, mk, sw, tb, a.MW, a.nc, lane);
+    const long f0 = (long)b * 1024 + lane;
+    float arg[16], sn[16], cs[16];
+    #pragma unroll
+    for (int r = 0; r < 16; r++) {
+        const long f = f0 + r * 64;
+        const float ch = a.chi[f < a.F ? f : 0];
+        arg[r] = v[r] * (ch * chs);
+    }
+    tile_sincos(arg, sn, cs);
+    // ---- middle: t_f = (float)u_f * chi[f] (x the folded normaliser: exact)
+    #pragma unroll
+    for (int r = 0; r < 16; r++) {
+        const long f = f0 + r * 64;
+        const bool in = f < a.F && f < hcols;
+        const long fc = in ? f : 0;
+        const double w0 = wrow[2 * fc], w1 = wrow[2 * fc + 1];
+        const double wc = (in && !(a.fit_intercept && f == 0)) ? w0 : 0.0;
+        const double ws = in ? w1 : 0.0;
+        const double u = scale * (ws * (double)cs[r] - wc * (double)sn[r]);
+        const float bk = in ? a.chi[fc] * a.chi_scale : 0.0f;
+        v[r] = (float)u * bk;
+    }
+    // ---- backward: H, D2, H, D1, H, D0 on every repetition of the tile
+    #pragma unroll
+    for (int s = 2; s >= 0; s--) {
+        wave_fht<LOG2P>(v, lane);
+        uint64_t m[16];
+        #pragma unroll
+        for (int r = 0; r < 16; r++) m[r] = mk[(long)s * a.MW + r];
+        #pragma unroll
+        for (int r = 0; r < 16; r++) {
+            const float t = (LOG2P & 1) ? v[r] * a.nc : v[r];
+            v[r] = __builtin_amdgcn_inverse_ballot_w64(m[r]) ? -t : t;
+        }
+    }
+}
+
 template <int LOG2P>
 __global__ __launch_bounds__(256) void rbf_input_grad_kernel(InputGradArgs a) {
     constexpr int P = 1 << LOG2P;
@@ -45,7 +96,6 @@ __global__ __launch_bounds__(256) void rbf_input_grad_kernel(InputGradArgs a) {
     float *tb = tbuf + wv * (TP ? TBUF_FLOATS : 1);
     const float *xrow = a.x + i * (long)a.d;
     const double *wrow = a.w + i * a.w_row_stride;
-    const long hcols = a.w_cols >> 1;                    // frequencies with a weight pair
     const float chs = TP ? a.chi_scale * sorf_kept_sign(lane) : a.chi_scale;     // the sign tile_sorf kept, into chi (exact)
     double acc[16];
     #pragma unroll
@@ -53,48 +103,9 @@ __global__ __launch_bounds__(256) void rbf_input_grad_kernel(InputGradArgs a) {
 
     for (int bb = wv; bb < a.nb; bb += 4) {
         const int b = __builtin_amdgcn_readfirstlane(bb);
-        const cmask_t mk = as_cmask(a.masks + (long)b * 16);
         float v[16];
-        // ---- forward: the feature operators' front end
         wave_load<LOG2P>(v, xrow, a.d, lane);
-        uint32_t sw[3] = {0, 0, 0};
-        if constexpr (TP) load_sign_words(sw, a.masks, a.MW, b, lane);
-        tile_sorf<LOG2P, TP, TP, false>(v, mk, sw, tb, a.MW, a.nc, lane);
-        const long f0 = (long)b * 1024 + lane;
-        float arg[16], sn[16], cs[16];
-        #pragma unroll
-        for (int r = 0; r < 16; r++) {
-            const long f = f0 + r * 64;
-            const float ch = a.chi[f < a.F ? f : 0];
-            arg[r] = v[r] * (ch * chs);
-        }
-        tile_sincos(arg, sn, cs);
-        // ---- middle: t_f = (float)u_f * chi[f] (x the folded normaliser: exact)
-        #pragma unroll
-        for (int r = 0; r < 16; r++) {
-            const long f = f0 + r * 64;
-            const bool in = f < a.F && f < hcols;
-            const long fc = in ? f : 0;
-            const double w0 = wrow[2 * fc], w1 = wrow[2 * fc + 1];
-            const double wc = (in && !(a.fit_intercept && f == 0)) ? w0 : 0.0;
-            const double ws = in ? w1 : 0.0;
-            const double u = a.scale * (ws * (double)cs[r] - wc * (double)sn[r]);
-            const float bk = in ? a.chi[fc] * a.chi_scale : 0.0f;
-            v[r] = (float)u * bk;
-        }
-        // ---- backward: H, D2, H, D1, H, D0 on every repetition of the tile
-        #pragma unroll
-        for (int s = 2; s >= 0; s--) {
-            wave_fht<LOG2P>(v, lane);
-            uint64_t m[16];
-            #pragma unroll
-            for (int r = 0; r < 16; r++) m[r] = mk[(long)s * a.MW + r];
-            #pragma unroll
-            for (int r = 0; r < 16; r++) {
-                const float t = (LOG2P & 1) ? v[r] * a.nc : v[r];
-                v[r] = __builtin_amdgcn_inverse_ballot_w64(m[r]) ? -t : t;
-            }
-        }
+        input_grad_tile<LOG2P>(v, a, wrow, a.scale, b, chs, tb, lane);
         #pragma unroll
         for (int r = 0; r < 16; r++) acc[r] += (double)v[r];
     }

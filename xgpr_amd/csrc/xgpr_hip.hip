@@ -47,6 +47,7 @@ typedef enum { ncclFloat64 = 8 } ncclDataType_t;
 #include "../../include/xgpr_hip.h"
 #include "../../include/xgpr_hip_pool.h"
 #include "../../include/xgpr_hip_input_grad.h"
+#include "../../include/xgpr_hip_seq_input_grad.h"
 
 namespace {
 
@@ -66,6 +67,7 @@ namespace {
 #include "cg_kernels.inc"
 #include "launchers.inc"
 #include "input_grad.inc"
+#include "seq_input_grad.inc"
 
 }  // namespace
 
@@ -522,6 +524,25 @@ int xgpr_rbf_input_grad_f32(const float *x, const double *w, double *g, const in
                             void *workspace, size_t workspace_bytes, void *stream) {
     return rbf_input_grad_impl(x, w, g, radem, chi, n, d, w_row_stride, w_cols, num_freqs, radem_shape2, sigma, fit_intercept,
                                workspace, workspace_bytes, stream);
+}
+
+// ---- include/xgpr_hip_seq_input_grad.h
+int xgpr_conv_input_grad_ok(long width, long num_freqs) { return conv_input_grad_ok_impl(width, num_freqs); }
+int xgpr_conv_token_input_grad_ok(long width, long vocab, long C) { return conv_token_input_grad_ok_impl(width, vocab, C); }
+int xgpr_conv_input_grad_f32(const float *x, const double *w, double *g, const int8_t *radem, const float *chi,
+                             const int32_t *seqlen_host, const int32_t *seqlen_dev, long n, long L, long C, long w_row_stride,
+                             long w_cols, long num_freqs, long radem_shape2, double sigma, int conv_width, int scaling_type,
+                             int fit_intercept, void *workspace, size_t workspace_bytes, void *stream) {
+    return seq_input_grad_impl(nullptr, false, x, w, g, radem, chi, seqlen_host, seqlen_dev, n, L, 0, C, w_row_stride, w_cols, num_freqs,
+                               radem_shape2, sigma, conv_width, scaling_type, fit_intercept, workspace, workspace_bytes, stream);
+}
+int xgpr_conv_token_input_grad_f32(const uint8_t *tokens, const float *table, const double *w, double *g, const int8_t *radem,
+                                   const float *chi, const int32_t *seqlen_host, const int32_t *seqlen_dev, long n, long L, long vocab,
+                                   long C, long w_row_stride, long w_cols, long num_freqs, long radem_shape2, double sigma,
+                                   int conv_width, int scaling_type, int fit_intercept, void *workspace, size_t workspace_bytes,
+                                   void *stream) {
+    return seq_input_grad_impl(tokens, true, table, w, g, radem, chi, seqlen_host, seqlen_dev, n, L, vocab, C, w_row_stride, w_cols,
+                               num_freqs, radem_shape2, sigma, conv_width, scaling_type, fit_intercept, workspace, workspace_bytes, stream);
 }
 
 int xgpr_selftest_lane_xor(int32_t *out, void *stream) {

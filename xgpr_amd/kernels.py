@@ -123,6 +123,47 @@ class KernelBase:
             input_y = torch.from_numpy(input_y)
         return xtrans, input_y.to(self.device, torch.float64)
 
+    # the weights argument of the input-gradient methods (SORFKernel, ConvSORFKernel)
+    def _input_grad_weights(self, weights, w_cols, n):
+        w = weights if isinstance(weights, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(weights))
+        w = w.to(self.device, torch.float64)
+        if w.dim() not in (1, 2) or (w.dim() == 2 and w.shape[0] != n):
+            raise RuntimeError("weights must be one vector, or one row per datapoint.")
+        if w.dim() == 1 or w.stride(1) != 1:
+            w = w.contiguous()
+        w_cols = min(w.shape[-1], self.num_rffs) if w_cols is None else int(w_cols)
+        if w_cols < 2 or w_cols % 2 or w_cols > min(w.shape[-1], self.num_rffs):
+            raise RuntimeError("w_cols must be even, >= 2 and within the weights and the features.")
+        return w, w_cols
+
+
+def composed_input_gradient(x_scaled, weights, w_cols, radem_diag, chi_arr, num_rffs, fit_intercept, sigma, scale):
+    """d/dx of ``features(x) @ weights`` for rows ``x_scaled`` [n, d] (float32, already multiplied by sigma) from existing device
+    operators, at every width: float64 features with the intercept OFF (with it on, column 0 no longer holds cos p_0) rescaled
+    from the operator's float-typed constant to ``scale``, chi (.) u zero-padded to whole transforms, three rounds of
+    { FHT ; signs x normaliser } in the order 2, 1, 0 as ``MiniARDKernel.precompute_weights`` applies them to the identity, the
+    sum over the transforms and the product with sigma.  ``weights`` one vector or one row per row of ``x_scaled``; under
+    ``fit_intercept`` column 0 carries no weight."""
+    n, d = x_scaled.shape
+    nf, p = num_rffs // 2, padded_dims(d)
+    nblocks = radem_diag.shape[2] // p
+    z = torch.empty((n, num_rffs), dtype=torch.float64, device=x_scaled.device)
+    ext.hipRBFFeatureGen(x_scaled, z, radem_diag, chi_arr, False)
+    z *= scale / float(np.float32(np.sqrt(1.0 / nf)))
+    h = w_cols // 2
+    wc, ws = weights[..., 0:w_cols:2].clone(), weights[..., 1:w_cols:2]
+    if fit_intercept:
+        wc[..., 0] = 0.
+    t = torch.zeros((n, nblocks * p), dtype=torch.float64, device=x_scaled.device)
+    t[:, :h] = (ws * z[:, 0:w_cols:2] - wc * z[:, 1:w_cols:2]) * chi_arr[:h].to(torch.float64)
+    t = t.reshape(n * nblocks, p)
+    norm_constant = 1.0 / (2.0 ** (np.log2(p) / 2.0))
+    radem = radem_diag.to(torch.float64)
+    for r in (2, 1, 0):
+        ext.hipFastHadamardTransform2D(t)
+        t = (t.view(n, nblocks, p) * (radem[r, 0].view(1, nblocks, p) * norm_constant)).reshape(n * nblocks, p)
+    return (t.view(n, nblocks, p).sum(dim=1)[:, :d] * sigma).contiguous()
+
 
 class SORFKernel(KernelBase):
     """RBF / Matern / Cauchy on fixed-length vectors."""
@@ -269,18 +310,6 @@ class SORFKernel(KernelBase):
         return z
 
     # ---- derivative of a weighted sum of the features with respect to the INPUT: the transposed SORF
-    def _input_grad_weights(self, weights, w_cols, n):
-        w = weights if isinstance(weights, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(weights))
-        w = w.to(self.device, torch.float64)
-        if w.dim() not in (1, 2) or (w.dim() == 2 and w.shape[0] != n):
-            raise RuntimeError("weights must be one vector, or one row per datapoint.")
-        if w.dim() == 1 or w.stride(1) != 1:
-            w = w.contiguous()
-        w_cols = min(w.shape[-1], self.num_rffs) if w_cols is None else int(w_cols)
-        if w_cols < 2 or w_cols % 2 or w_cols > min(w.shape[-1], self.num_rffs):
-            raise RuntimeError("w_cols must be even, >= 2 and within the weights and the features.")
-        return w, w_cols
-
     def input_gradient(self, input_x, weights, w_cols=None):
         """float64 device tensor [n, d]: d/dx of ``transform_x(x) @ weights`` at every row of the UNSCALED ``input_x``.
         ``weights`` float64, one vector [>= w_cols] for all rows or one row per datapoint [n, >= w_cols]; only the first
@@ -297,29 +326,9 @@ class SORFKernel(KernelBase):
         return self.input_gradient_composed(xs, w, w_cols)
 
     def input_gradient_composed(self, x_scaled, weights, w_cols):
-        """The same gradient from existing device operators, at every width: float64 features with the intercept OFF (with
-        it on, column 0 no longer holds cos p_0) rescaled by the ratio of the two constants, chi (.) u zero-padded to whole
-        transforms, three rounds of { FHT ; signs x normaliser } in the order 2, 1, 0 as ``MiniARDKernel.precompute_weights``
-        applies them to the identity, the sum over the transforms and the product with sigma."""
-        n, d = x_scaled.shape
-        nf, p = self.num_freqs, padded_dims(d)
-        nblocks = self.radem_diag.shape[2] // p
-        z = torch.empty((n, self.num_rffs), dtype=torch.float64, device=self.device)
-        ext.hipRBFFeatureGen(x_scaled, z, self.radem_diag, self.chi_arr, False)
-        z *= self.row_cache_params()[1] / float(np.float32(np.sqrt(1.0 / nf)))
-        h = w_cols // 2
-        wc, ws = weights[..., 0:w_cols:2].clone(), weights[..., 1:w_cols:2]
-        if self.fit_intercept:
-            wc[..., 0] = 0.
-        t = torch.zeros((n, nblocks * p), dtype=torch.float64, device=self.device)
-        t[:, :h] = (ws * z[:, 0:w_cols:2] - wc * z[:, 1:w_cols:2]) * self.chi_arr[:h].to(torch.float64)
-        t = t.reshape(n * nblocks, p)
-        norm_constant = 1.0 / (2.0 ** (np.log2(p) / 2.0))
-        radem = self.radem_diag.to(torch.float64)
-        for r in (2, 1, 0):
-            ext.hipFastHadamardTransform2D(t)
-            t = (t.view(n, nblocks, p) * (radem[r, 0].view(1, nblocks, p) * norm_constant)).reshape(n * nblocks, p)
-        return (t.view(n, nblocks, p).sum(dim=1)[:, :d] * float(self.hyperparams[1])).contiguous()
+        """The same gradient from existing device operators, at every width (``composed_input_gradient``)."""
+        return composed_input_gradient(x_scaled, weights, w_cols, self.radem_diag, self.chi_arr, self.num_rffs, self.fit_intercept,
+                                       float(self.hyperparams[1]), self.row_cache_params()[1])
 
     def fused_ok(self):
         """The fused kernels cover padded width <= 4096 (single pass up to num_freqs = 7168 -- 4096 at padded widths
@@ -466,6 +475,79 @@ class ConvSORFKernel(KernelBase):
             return
         ext.hipConvFeatureRows(x_scaled, rows_out, self.radem_diag, self.chi_arr, lengths, self.conv_width, self.scaling_type,
                                self.fit_intercept)
+
+    # ---- derivative of a weighted sum of the features with respect to the INPUT, per position and channel
+    COMPOSED_GRAD_ELEMS = 1 << 25    # float64 elements of per-window weights (or window rows) the unfold route holds per slice
+
+    def input_gradient(self, input_x, sequence_length, weights, w_cols=None):
+        """float64 device tensor [n, L, C]: d/dx of ``transform_x(x, sequence_length) @ weights`` at every position and channel of
+        the UNSCALED sequences ``input_x`` (dense [n, L, C], or a TokenBatch: the gradient is then with respect to the table rows
+        the tokens select, position by position -- a saliency map).  Positions past a sequence's length are exactly 0.
+        ``weights`` and ``w_cols`` as for ``SORFKernel.input_gradient``.  One HIP kernel where ``ext.conv_input_grad_ok`` /
+        ``ext.conv_token_input_grad_ok`` hold (windows of up to 1024 elements; a token table the LDS image holds); tokens over a
+        larger table are expanded slice by slice, wider windows take ``input_gradient_composed``."""
+        xs = self.scaled_f32(input_x)
+        lengths = self._host_lengths(xs, sequence_length)
+        n, L, C = xs.shape
+        w, w_cols = self._input_grad_weights(weights, w_cols, n)
+        sigma = float(self.hyperparams[1])
+        if isinstance(xs, TokenBatch):
+            out = torch.empty((n, L, C), dtype=torch.float64, device=self.device)
+            if (xs.is_cuda and xs.tokens.is_contiguous()
+                    and ext.conv_token_input_grad_ok(self.conv_width * C, xs.table.shape[0], C) == 1):
+                ext.hipConvTokenInputGrad(xs.tokens, xs.table, w, out, self.radem_diag, self.chi_arr, lengths, sigma,
+                                          self.conv_width, self.scaling_type, self.fit_intercept, w_cols=w_cols)
+                return out
+            for lo, hi, xd, lens in self._dense_slices(xs, lengths):
+                out[lo:hi] = self._dense_input_gradient(xd, lens, w if w.dim() == 1 else w[lo:hi], w_cols)
+            return out
+        return self._dense_input_gradient(xs, lengths, w, w_cols)
+
+    def _dense_input_gradient(self, x_scaled, lengths, w, w_cols):
+        if ext.conv_input_grad_ok(self.conv_width * x_scaled.shape[2], self.num_freqs) != 1:
+            return self.input_gradient_composed(x_scaled, lengths, w, w_cols)
+        out = torch.empty(tuple(x_scaled.shape), dtype=torch.float64, device=self.device)
+        ext.hipConvInputGrad(x_scaled, w, out, self.radem_diag, self.chi_arr, lengths, float(self.hyperparams[1]), self.conv_width,
+                             self.scaling_type, self.fit_intercept, w_cols=w_cols)
+        return out
+
+    def input_gradient_composed(self, x_scaled, lengths, weights, w_cols):
+        """The same gradient by the unfold route, at every window width, from existing operators: a bounded slice of sequences
+        is unfolded into its L - conv_width + 1 window rows each, the rows go to ``hipRBFInputGrad`` (``composed_input_gradient``
+        beyond its widths) with per-row weights already divided by the sequence's k-mer normaliser -- zero for the windows past a
+        sequence's last k-mer --, and the rows' gradients are folded back with conv_width slice additions in float64, window
+        offset 0 first.  ``x_scaled`` dense float32 [n, L, C], already multiplied by sigma; ``lengths`` int32 on the host."""
+        n, L, C = x_scaled.shape
+        cw, nf, sigma = self.conv_width, self.num_freqs, float(self.hyperparams[1])
+        d, nkmax = cw * C, L - cw + 1
+        if int(lengths.min()) < cw or int(lengths.max()) > L:
+            raise RuntimeError("All sequence lengths must be >= conv width and < array size.")
+        nk = torch.from_numpy(lengths.astype(np.float64) - (cw - 1)).to(self.device)
+        scale = float(np.sqrt(1.0 / nf))
+        direct = ext.rbf_input_grad_ok(d, nf) == 1
+        # the row operator's constant with the intercept off is the float-typed sqrt(1 / F): the ratio to this kernel's rides on the weights
+        ratio = scale / float(np.float32(np.sqrt(1.0 / nf))) if direct else 1.0
+        norm = (torch.ones_like(nk), torch.sqrt(nk), nk)[self.scaling_type] / ratio
+        live = torch.arange(nkmax, device=self.device)[None, :] < nk[:, None]             # [n, nkmax]: window j is a k-mer
+        out = torch.zeros((n, L, C), dtype=torch.float64, device=self.device)
+        step = max(1, self.COMPOSED_GRAD_ELEMS // (nkmax * max(w_cols, padded_dims(d))))
+        for lo in range(0, n, step):
+            hi = min(lo + step, n)
+            rows = x_scaled[lo:hi].unfold(1, cw, 1).permute(0, 1, 3, 2).reshape((hi - lo) * nkmax, d).contiguous()
+            wseq = (weights[None, :w_cols] if weights.dim() == 1 else weights[lo:hi, :w_cols]) / norm[lo:hi, None]
+            wrows = (wseq[:, None, :] * live[lo:hi, :, None]).reshape((hi - lo) * nkmax, w_cols)
+            if self.fit_intercept:
+                wrows[:, 0] = 0.
+            if direct:
+                g = torch.empty((rows.shape[0], d), dtype=torch.float64, device=self.device)
+                ext.hipRBFInputGrad(rows, wrows, g, self.radem_diag, self.chi_arr, sigma, False, w_cols=w_cols)
+            else:
+                g = composed_input_gradient(rows, wrows, w_cols, self.radem_diag, self.chi_arr, self.num_rffs, False, sigma, scale)
+            g = g.view(hi - lo, nkmax, cw, C)
+            for q in range(cw):
+                out[lo:hi, q:q + nkmax, :] += g[:, :, q, :]
+        out *= (torch.arange(L, device=self.device)[None, :] < torch.from_numpy(lengths).to(self.device)[:, None])[:, :, None]
+        return out
 
     def grad_rows_ok(self):
         """Whether ``fill_grad_rows`` can write this kernel's float32 feature AND gradient rows, and the exact NMLL

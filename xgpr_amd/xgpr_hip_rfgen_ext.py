@@ -928,6 +928,26 @@ def ztz_matvec_plan(d, num_freqs):
     return int(_LIB.xgpr_ztz_matvec_plan(int(d), int(num_freqs)))
 
 
+def _grad_weights(weights, n):
+    """(row stride for the C ABI, columns available) of an input-gradient weight argument: 1-d, one vector for all rows (stride
+    0), or 2-d [n, stride] with unit column stride."""
+    if not isinstance(weights, torch.Tensor) or not weights.is_cuda or weights.dtype != torch.float64:
+        raise TypeError("weights: expected a float64 device tensor")
+    if weights.dim() == 1:
+        if not weights.is_contiguous():
+            raise TypeError("weights: expected a C-contiguous array")
+        stride, avail = 0, weights.shape[0]
+    elif weights.dim() == 2:
+        if weights.shape[0] != n:
+            raise RuntimeError("Wrong array sizes.")
+        if weights.stride(1) != 1 or (n > 1 and weights.stride(0) < weights.shape[1]):
+            raise TypeError("weights: expected rows of contiguous float64 values")
+        stride, avail = (weights.stride(0) if n > 1 else weights.shape[1]), weights.shape[1]
+    else:
+        raise TypeError("weights: expected 1 or 2 dims")
+    return stride, avail
+
+
 def rbf_input_grad_ok(d, num_freqs):
     """Whether hipRBFInputGrad's kernel serves an input of ``d`` columns (padded width up to 1024); no device work."""
     return int(_LIB.xgpr_rbf_input_grad_ok(int(d), int(num_freqs)))
@@ -946,20 +966,7 @@ def hipRBFInputGrad(x_scaled, weights, out, radem, chi, sigma, fit_intercept, w_
     n, d = x_scaled.shape
     if tuple(out.shape) != (n, d):
         raise RuntimeError("Wrong array sizes.")
-    if not isinstance(weights, torch.Tensor) or not weights.is_cuda or weights.dtype != torch.float64:
-        raise TypeError("weights: expected a float64 device tensor")
-    if weights.dim() == 1:
-        if not weights.is_contiguous():
-            raise TypeError("weights: expected a C-contiguous array")
-        stride, avail = 0, weights.shape[0]
-    elif weights.dim() == 2:
-        if weights.shape[0] != n:
-            raise RuntimeError("Wrong array sizes.")
-        if weights.stride(1) != 1 or (n > 1 and weights.stride(0) < weights.shape[1]):
-            raise TypeError("weights: expected rows of contiguous float64 values")
-        stride, avail = (weights.stride(0) if n > 1 else weights.shape[1]), weights.shape[1]
-    else:
-        raise TypeError("weights: expected 1 or 2 dims")
+    stride, avail = _grad_weights(weights, n)
     w_cols = 2 * chi.shape[0] if w_cols is None else int(w_cols)
     if w_cols > avail:
         raise RuntimeError("Wrong array sizes.")
@@ -970,6 +977,74 @@ def hipRBFInputGrad(x_scaled, weights, out, radem, chi, sigma, fit_intercept, w_
     return _lib.check(_LIB.xgpr_rbf_input_grad_f32(
         x, C.c_void_p(weights.data_ptr()), g, r, c, n, d, stride, w_cols, chi.shape[0], radem.shape[2], float(sigma),
         int(bool(fit_intercept)), wp, wn, _stream()))
+
+
+def conv_input_grad_ok(width, num_freqs):
+    """Whether hipConvInputGrad's kernel serves a window of ``width`` = conv_width * C elements (padded width up to 1024)."""
+    return int(_LIB.xgpr_conv_input_grad_ok(int(width), int(num_freqs)))
+
+
+def conv_token_input_grad_ok(width, vocab, C):
+    """Whether hipConvTokenInputGrad serves the window and holds a table of ``vocab`` rows and ``C`` columns in LDS."""
+    return int(_LIB.xgpr_conv_token_input_grad_ok(int(width), int(vocab), int(C)))
+
+
+def _seq_grad_tail(weights, n, chi, radem, w_cols, workspace, device):
+    stride, avail = _grad_weights(weights, n)
+    w_cols = 2 * chi.shape[0] if w_cols is None else int(w_cols)
+    if w_cols > avail:
+        raise RuntimeError("Wrong array sizes.")
+    if workspace is None:
+        ws, wp, wn = _workspace(_LIB.xgpr_rbf_workspace_bytes(radem.shape[2]), device)
+    else:
+        ws, wp, wn = workspace, C.c_void_p(workspace.data_ptr()), C.c_size_t(workspace.numel() * workspace.element_size())
+    return stride, w_cols, ws, wp, wn
+
+
+def hipConvInputGrad(x_scaled, weights, out, radem, chi, seqlen, sigma, conv_width, scaling_type, fit_intercept, w_cols=None,
+                     workspace=None):
+    """``out[n, L, C]`` (float64, OVERWRITTEN; exactly 0.0 at positions past a sequence's length) <- d/dx of
+    ``features(x) @ weights`` for the sequence and graph kernels (include/xgpr_hip_seq_input_grad.h): the transposed SORF of
+    every k-mer window, overlap-added per position.  ``x_scaled`` [n, L, C] float32 is already multiplied by sigma; ``weights``,
+    ``w_cols`` and ``fit_intercept`` as for hipRBFInputGrad; ``seqlen`` int32 on the host."""
+    x = _dev(x_scaled, "x_scaled", torch.float32, 3)
+    g = _dev(out, "out", torch.float64, 3)
+    r = _radem3(radem)
+    c = _dev(chi, "chi", torch.float32, 1)
+    n, L, ch = x_scaled.shape
+    if tuple(out.shape) != (n, L, ch):
+        raise RuntimeError("Wrong array sizes.")
+    host, dev = _seqlens(seqlen, x_scaled.device)
+    if host.shape[0] != n:
+        raise RuntimeError("wrong array sizes")
+    stride, w_cols, ws, wp, wn = _seq_grad_tail(weights, n, chi, radem, w_cols, workspace, x_scaled.device)
+    return _lib.check(_LIB.xgpr_conv_input_grad_f32(
+        x, C.c_void_p(weights.data_ptr()), g, r, c, C.c_void_p(host.ctypes.data), C.c_void_p(dev.data_ptr()), n, L, ch, stride,
+        w_cols, chi.shape[0], radem.shape[2], float(sigma), int(conv_width), int(scaling_type), int(bool(fit_intercept)), wp, wn,
+        _stream()))
+
+
+def hipConvTokenInputGrad(tokens, table, weights, out, radem, chi, seqlen, sigma, conv_width, scaling_type, fit_intercept,
+                          w_cols=None, workspace=None):
+    """hipConvInputGrad for sequences given as tokens: ``tokens`` [n, L] uint8 index the rows of ``table`` [V, C] float32
+    (already sigma-scaled); ``out`` [n, L, C] receives exactly what hipConvInputGrad writes for ``table[tokens]``.  Shapes for
+    which ``conv_token_input_grad_ok`` is 0 raise RuntimeError and launch nothing."""
+    t = _dev(tokens, "tokens", torch.uint8, 2)
+    tab = _dev(table, "table", torch.float32, 2)
+    g = _dev(out, "out", torch.float64, 3)
+    r = _radem3(radem)
+    c = _dev(chi, "chi", torch.float32, 1)
+    n, L = tokens.shape
+    if tuple(out.shape) != (n, L, table.shape[1]):
+        raise RuntimeError("Wrong array sizes.")
+    host, dev = _seqlens(seqlen, tokens.device)
+    if host.shape[0] != n:
+        raise RuntimeError("wrong array sizes")
+    stride, w_cols, ws, wp, wn = _seq_grad_tail(weights, n, chi, radem, w_cols, workspace, tokens.device)
+    return _lib.check(_LIB.xgpr_conv_token_input_grad_f32(
+        t, tab, C.c_void_p(weights.data_ptr()), g, r, c, C.c_void_p(host.ctypes.data), C.c_void_p(dev.data_ptr()), n, L,
+        table.shape[0], table.shape[1], stride, w_cols, chi.shape[0], radem.shape[2], float(sigma), int(conv_width),
+        int(scaling_type), int(bool(fit_intercept)), wp, wn, _stream()))
 
 
 def selftest_lane_xor(device="cuda"):
