@@ -109,6 +109,14 @@ SEQ_INPUT_GRAD_SIGNATURES = {
     "xgpr_conv_token_input_grad_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _l, _l, _l, _l, _l, _l, _l, _l, _d, _i, _i, _i, _vp,
                                        _sz, _vp],
 }
+# ... and include/xgpr_hip_pool_input_grad.h, the fifth (tests/test_pool_input_grad_host.py)
+POOL_INPUT_GRAD_SIGNATURES = {
+    "xgpr_conv_maxpool_input_grad_ok": [_l],
+    "xgpr_conv_token_maxpool_input_grad_ok": [_l, _l, _l],
+    "xgpr_conv_maxpool_input_grad_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _l, _l, _l, _l, _l, _l, _i, _vp, _sz, _vp],
+    "xgpr_conv_token_maxpool_input_grad_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _l, _l, _l, _l, _l, _l, _l, _i, _vp,
+                                               _sz, _vp],
+}
 STRING_FUNCS = ["xgpr_last_error", "xgpr_build_arch", "xgpr_build_id"]
 
 _lib = None
@@ -128,7 +136,7 @@ def load():
             "(run `python xgpr_amd/build.py`); xgpr_amd has no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
     for name, args in (list(SIGNATURES.items()) + list(POOL_SIGNATURES.items()) + list(INPUT_GRAD_SIGNATURES.items())
-                       + list(SEQ_INPUT_GRAD_SIGNATURES.items())):
+                       + list(SEQ_INPUT_GRAD_SIGNATURES.items()) + list(POOL_INPUT_GRAD_SIGNATURES.items())):
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = C.c_int

@@ -31,6 +31,43 @@ struct InputGradArgs {
     double sigma;
 };
 
+// The backward half of a tile, shared by input_grad_tile below and the max-pool backward (pool_input_grad.inc): H, D2, H, D1, H, D0
+// on every repetition of the tile in layout C.  On entry v holds t_f = (float)u_f * chi[f] (x the folded normaliser).
+template <int LOG2P>
+__device__ __forceinline__ void input_grad_backward(float (&v)[16], const cmask_t mk, int MW, float nc, int lane) {
+    #pragma unroll
+    for (int s = 2; s >= 0; s--) {
+        wave_fht<LOG2P>(v, lane);
+        uint64_t m[16];
+        #pragma unroll
+        for (int r = 0; r < 16; r++) m[r] = mk[(long)s * MW + r];
+        #pragma unroll
+        for (int r = 0; r < 16; r++) {
+            const float t = (LOG2P & 1) ? v[r] * nc : v[r];
+            v[r] = __builtin_amdgcn_inverse_ballot_w64(m[r]) ? -t : t;
+        }
+    }
+}
+
+// The forward half of a tile, shared the same way: tile_sorf on the tile the caller loaded (layout C), then the projections
+// arg_f = v_f * (chi[f] * chs) exactly as the feature and max-pool operators form them (frequencies >= F take chi[0]: never used).
+// mk: the tile's packed sign masks, as_cmask(a.masks + 16 b).
+template <int LOG2P>
+__device__ __forceinline__ void input_grad_forward(float (&v)[16], float (&arg)[16], const InputGradArgs &a, const cmask_t mk, int b,
+                                                   float chs, float *tb, int lane) {
+    constexpr bool TP = LOG2P >= 7;
+    uint32_t sw[3] = {0, 0, 0};
+    if constexpr (TP) load_sign_words(sw, a.masks, a.MW, b, lane);
+    tile_sorf<LOG2P, TP, TP, false>(v, mk, sw, tb, a.MW, a.nc, lane);
+    const long f0 = (long)b * 1024 + lane;
+    #pragma unroll
+    for (int r = 0; r < 16; r++) {
+        const long f = f0 + r * 64;
+        const float ch = a.chi[f < a.F ? f : 0];
+        arg[r] = v[r] * (ch * chs);
+    }
+}
+
 // One tile (1024 frequencies, tile b) of the gradient, shared by the fixed-vector kernel below and the sequence kernel
 // (seq_input_grad.inc).  On entry v holds the sigma-scaled row -- or k-mer window -- replicated over the tile's 1024 / P transforms
 // (wave_load's layout C); on return it holds the tile's part of W^T u in layout C, every repetition on its own.  `scale` is the
@@ -38,21 +75,12 @@ struct InputGradArgs {
 template <int LOG2P>
 __device__ __forceinline__ void input_grad_tile(float (&v)[16], const InputGradArgs &a, const double *wrow, double scale, int b, float chs,
                                                 float *tb, int lane) {
-    constexpr bool TP = LOG2P >= 7;
     const long hcols = a.w_cols >> 1;                    // frequencies with a weight pair
     const cmask_t mk = as_cmask(a.masks + (long)b * 16);
     // ---- forward: the feature operators' front end (the tile is loaded by the caller)
-    uint32_t sw[3] = {0, 0, 0};
-    if constexpr (TP) load_sign_words(sw, a.masks, a.MW, b, lane);
-    tile_sorf<LOG2P, TP, TP, false>(v, mk, sw, tb, a.MW, a.nc, lane);
-    const long f0 = (long)b * 1024 + lane;
     float arg[16], sn[16], cs[16];
-    #pragma unroll
-    for (int r = 0; r < 16; r++) {
-        const long f = f0 + r * 64;
-        const float ch = a.chi[f < a.F ? f : 0];
-        arg[r] = v[r] * (ch * chs);
-    }
+    input_grad_forward<LOG2P>(v, arg, a, mk, b, chs, tb, lane);
+    const long f0 = (long)b * 1024 + lane;
     tile_sincos(arg, sn, cs);
     // ---- middle: t_f = (float)u_f * chi[f] (x the folded normaliser: exact)
     #pragma unroll
@@ -68,18 +96,7 @@ __device__ __forceinline__ void input_grad_tile(float (&v)[16], const InputGradA
         v[r] = (float)u * bk;
     }
     // ---- backward: H, D2, H, D1, H, D0 on every repetition of the tile
-    #pragma unroll
-    for (int s = 2; s >= 0; s--) {
-        wave_fht<LOG2P>(v, lane);
-        uint64_t m[16];
-        #pragma unroll
-        for (int r = 0; r < 16; r++) m[r] = mk[(long)s * a.MW + r];
-        #pragma unroll
-        for (int r = 0; r < 16; r++) {
-            const float t = (LOG2P & 1) ? v[r] * a.nc : v[r];
-            v[r] = __builtin_amdgcn_inverse_ballot_w64(m[r]) ? -t : t;
-        }
-    }
+    input_grad_backward<LOG2P>(v, mk, a.MW, a.nc, lane);
 }
 
 template <int LOG2P>

@@ -27,10 +27,24 @@ struct SeqInputGradArgs {
     int L; int scaling_type;
 };
 
-template <int LOG2P, class WIN>
-__device__ __forceinline__ void seq_input_grad_body(const SeqInputGradArgs &s, WIN &win) {
+// What a tile contributes for k-mer j is a policy of the overlap-add body below (TILE): operator()(v, &cur, j, b, tb, lane) leaves the
+// tile's part of W^T u_j in v (layout C) and returns false where the tile adds nothing for this k-mer (wave-uniform).  SeqGradTile is
+// the sequence kernels' tile, input_grad_tile on the held window; the max-pool backward (pool_input_grad.inc) brings its own.
+template <int LOG2P> struct SeqGradTile {
+    static constexpr bool WINDOWS = true;               // the tile reads the k-mer windows
+    const InputGradArgs &a; const double *wrow; double rs; float chs;
+    template <class WIN>
+    __device__ __forceinline__ bool operator()(float (&v)[16], const WIN *cur, int, int b, float *tb, int lane) const {
+        cur->take(v);
+        input_grad_tile<LOG2P>(v, a, wrow, rs, b, chs, tb, lane);
+        return true;
+    }
+};
+
+// The k-mer loop, the cross-wave meeting, the ring and the stores of one sequence (blockIdx.x), for any TILE.
+template <int LOG2P, class WIN, class TILE>
+__device__ __forceinline__ void seq_overlap_add_body(const SeqInputGradArgs &s, WIN &win, const TILE &tile, float *tb) {
     constexpr int P = 1 << LOG2P;
-    constexpr bool TP = LOG2P >= 7;
     constexpr int RP = P >= 64 ? P / 64 : 1;            // registers that hold distinct window elements (layout C)
     constexpr int RED = P >= 64 ? P : 64;
     constexpr int NE = (P + 255) / 256;                 // window elements per thread in the overlap-add
@@ -38,18 +52,11 @@ __device__ __forceinline__ void seq_input_grad_body(const SeqInputGradArgs &s, W
     const int lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const long i = blockIdx.x;
-    __shared__ __attribute__((aligned(16))) float tbuf[TP ? 4 * TBUF_FLOATS : 4];
     __shared__ double red[4][RED];
     __shared__ double ring[RED];
-    float *tb = tbuf + wv * (TP ? TBUF_FLOATS : 1);
     const int C = s.win.kmer_stride, cw = s.win.conv_width, d = a.d;
     const int len = s.win.seqlen[i];
     const int nk = len - cw + 1;
-    const double *wrow = a.w + i * a.w_row_stride;
-    const float chs = TP ? a.chi_scale * sorf_kept_sign(lane) : a.chi_scale;     // the sign tile_sorf kept, into chi (exact)
-    double rs = a.scale;
-    if (s.scaling_type == 1) rs = a.scale / sqrt((double)nk);
-    else if (s.scaling_type == 2) rs = a.scale / (double)nk;
     double *grow = a.g + i * (long)s.L * C;
 
     // window element e = threadIdx.x + 256 k of this thread: position offset q, channel c (no division in the k-mer loop)
@@ -61,23 +68,29 @@ __device__ __forceinline__ void seq_input_grad_body(const SeqInputGradArgs &s, W
         if (e < d) ring[e] = 0.0;      // (ordered before the first add by the barrier in front of it)
     }
 
-    win.begin(s.win, i, lane);
-    win.issue(0);
+    if constexpr (TILE::WINDOWS) {
+        win.begin(s.win, i, lane);
+        win.issue(0);
+    }
     int jm = 0;                                          // j mod conv_width
     for (int j = 0; j < nk; j++) {
-        WIN cur = win;                                   // window j; the next one is fetched under this one's transforms
-        win.issue(j + 1 < nk ? j + 1 : j);
         double acc[16];
         #pragma unroll
         for (int r = 0; r < 16; r++) acc[r] = 0.0;
-        for (int bb = wv; bb < a.nb; bb += 4) {
-            const int b = __builtin_amdgcn_readfirstlane(bb);
-            float v[16];
-            cur.take(v);
-            input_grad_tile<LOG2P>(v, a, wrow, rs, b, chs, tb, lane);
-            #pragma unroll
-            for (int r = 0; r < 16; r++) acc[r] += (double)v[r];
-        }
+        auto owned_tiles = [&](const WIN *cur) {
+            for (int bb = wv; bb < a.nb; bb += 4) {
+                const int b = __builtin_amdgcn_readfirstlane(bb);
+                float v[16];
+                if (!tile(v, cur, j, b, tb, lane)) continue;
+                #pragma unroll
+                for (int r = 0; r < 16; r++) acc[r] += (double)v[r];
+            }
+        };
+        if constexpr (TILE::WINDOWS) {
+            WIN cur = win;                               // window j; the next one is fetched under this one's transforms
+            win.issue(j + 1 < nk ? j + 1 : j);
+            owned_tiles(&cur);
+        } else owned_tiles(nullptr);                     // (a tile that reads no window is handed none)
         // ---- the repetitions of a tile: element e of the tile is window element e mod P
         #pragma unroll
         for (int r = RP; r < 16; r++) acc[r & (RP - 1)] += acc[r];
@@ -114,6 +127,23 @@ __device__ __forceinline__ void seq_input_grad_body(const SeqInputGradArgs &s, W
         const int q = e / C, c = e - q * C, l = nk + q;
         grow[(long)l * C + c] = l < len ? ring[(l % cw) * C + c] * a.sigma : 0.0;
     }
+}
+
+template <int LOG2P, class WIN>
+__device__ __forceinline__ void seq_input_grad_body(const SeqInputGradArgs &s, WIN &win) {
+    constexpr bool TP = LOG2P >= 7;
+    __shared__ __attribute__((aligned(16))) float tbuf[TP ? 4 * TBUF_FLOATS : 4];
+    float *tb = tbuf + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) * (TP ? TBUF_FLOATS : 1);
+    const InputGradArgs &a = s.ig;
+    const int lane = threadIdx.x & 63;
+    const long i = blockIdx.x;
+    const int nk = s.win.seqlen[i] - s.win.conv_width + 1;
+    const float chs = TP ? a.chi_scale * sorf_kept_sign(lane) : a.chi_scale;     // the sign tile_sorf kept, into chi (exact)
+    double rs = a.scale;
+    if (s.scaling_type == 1) rs = a.scale / sqrt((double)nk);
+    else if (s.scaling_type == 2) rs = a.scale / (double)nk;
+    const SeqGradTile<LOG2P> tile = {a, a.w + i * a.w_row_stride, rs, chs};
+    seq_overlap_add_body<LOG2P>(s, win, tile, tb);
 }
 
 template <int LOG2P>

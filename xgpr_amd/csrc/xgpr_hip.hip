@@ -48,6 +48,7 @@ typedef enum { ncclFloat64 = 8 } ncclDataType_t;
 #include "../../include/xgpr_hip_pool.h"
 #include "../../include/xgpr_hip_input_grad.h"
 #include "../../include/xgpr_hip_seq_input_grad.h"
+#include "../../include/xgpr_hip_pool_input_grad.h"
 
 namespace {
 
@@ -68,6 +69,7 @@ namespace {
 #include "launchers.inc"
 #include "input_grad.inc"
 #include "seq_input_grad.inc"
+#include "pool_input_grad.inc"
 
 }  // namespace
 
@@ -543,6 +545,25 @@ int xgpr_conv_token_input_grad_f32(const uint8_t *tokens, const float *table, co
                                    void *stream) {
     return seq_input_grad_impl(tokens, true, table, w, g, radem, chi, seqlen_host, seqlen_dev, n, L, vocab, C, w_row_stride, w_cols,
                                num_freqs, radem_shape2, sigma, conv_width, scaling_type, fit_intercept, workspace, workspace_bytes, stream);
+}
+
+// ---- include/xgpr_hip_pool_input_grad.h
+int xgpr_conv_maxpool_input_grad_ok(long width) { return conv_maxpool_input_grad_ok_impl(width); }
+int xgpr_conv_token_maxpool_input_grad_ok(long width, long vocab, long C) { return conv_token_maxpool_input_grad_ok_impl(width, vocab, C); }
+int xgpr_conv_maxpool_input_grad_f32(const float *x, const double *g, double *out, int32_t *argmax, const int8_t *radem,
+                                     const float *chi, const int32_t *seqlen_host, const int32_t *seqlen_dev, long n, long L, long C,
+                                     long g_row_stride, long num_freqs, long radem_shape2, int conv_width, void *workspace,
+                                     size_t workspace_bytes, void *stream) {
+    return pool_input_grad_impl(nullptr, false, x, g, out, argmax, radem, chi, seqlen_host, seqlen_dev, n, L, 0, C, g_row_stride,
+                                num_freqs, radem_shape2, conv_width, workspace, workspace_bytes, stream);
+}
+int xgpr_conv_token_maxpool_input_grad_f32(const uint8_t *tokens, const float *table, const double *g, double *out, int32_t *argmax,
+                                           const int8_t *radem, const float *chi, const int32_t *seqlen_host,
+                                           const int32_t *seqlen_dev, long n, long L, long vocab, long C, long g_row_stride,
+                                           long num_freqs, long radem_shape2, int conv_width, void *workspace, size_t workspace_bytes,
+                                           void *stream) {
+    return pool_input_grad_impl(tokens, true, table, g, out, argmax, radem, chi, seqlen_host, seqlen_dev, n, L, vocab, C, g_row_stride,
+                                num_freqs, radem_shape2, conv_width, workspace, workspace_bytes, stream);
 }
 
 int xgpr_selftest_lane_xor(int32_t *out, void *stream) {

@@ -156,13 +156,21 @@ def composed_input_gradient(x_scaled, weights, w_cols, radem_diag, chi_arr, num_
         wc[..., 0] = 0.
     t = torch.zeros((n, nblocks * p), dtype=torch.float64, device=x_scaled.device)
     t[:, :h] = (ws * z[:, 0:w_cols:2] - wc * z[:, 1:w_cols:2]) * chi_arr[:h].to(torch.float64)
+    return (transposed_sorf_rows(t, radem_diag, p)[:, :d] * sigma).contiguous()
+
+
+def transposed_sorf_rows(t, radem_diag, p):
+    """The backward half of ``composed_input_gradient``, shared with ``Conv1dTwoLayerKernel.first_layer_gradient_composed``:
+    ``t`` [n, nblocks * p] float64 holds chi (.) u zero-padded to whole transforms; three rounds of { FHT ; signs x normaliser }
+    in the order 2, 1, 0, then the sum over the transforms -> [n, p]."""
+    n, nblocks = t.shape[0], t.shape[1] // p
     t = t.reshape(n * nblocks, p)
     norm_constant = 1.0 / (2.0 ** (np.log2(p) / 2.0))
     radem = radem_diag.to(torch.float64)
     for r in (2, 1, 0):
         ext.hipFastHadamardTransform2D(t)
         t = (t.view(n, nblocks, p) * (radem[r, 0].view(1, nblocks, p) * norm_constant)).reshape(n * nblocks, p)
-    return (t.view(n, nblocks, p).sum(dim=1)[:, :d] * sigma).contiguous()
+    return t.view(n, nblocks, p).sum(dim=1)
 
 
 class SORFKernel(KernelBase):
@@ -729,6 +737,24 @@ class LinearKernel:
         xtrans = self.transform_x(input_x)
         return xtrans, torch.zeros((xtrans.shape[0], 0, 0), dtype=torch.float64, device=self.device)
 
+    def input_gradient(self, input_x, weights, w_cols=None):
+        """float64 device tensor [n, d]: d/dx of ``transform_x(x) @ weights`` -- the weight columns that multiply x (the
+        intercept column is skipped), one vector for all rows or one row per datapoint; feature columns at or beyond
+        ``w_cols`` carry no weight.  The features are the input itself, so there is no operator to run."""
+        n, d = input_x.shape[0], self._xdim[1]
+        w = weights if isinstance(weights, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(weights))
+        w = w.to(self.device, torch.float64)
+        if w.dim() not in (1, 2) or (w.dim() == 2 and w.shape[0] != n):
+            raise RuntimeError("weights must be one vector, or one row per datapoint.")
+        w_cols = min(w.shape[-1], self.num_rffs) if w_cols is None else int(w_cols)
+        if w_cols < 1 or w_cols > min(w.shape[-1], self.num_rffs):
+            raise RuntimeError("w_cols must be >= 1 and within the weights and the features.")
+        first = 1 if self.fit_intercept else 0
+        out = torch.zeros((n, d), dtype=torch.float64, device=self.device)
+        if w_cols > first:
+            out[:, :w_cols - first] = w[..., first:w_cols]
+        return out
+
 
 class Conv1dTwoLayerKernel(KernelBase):
     """kernels/convolution_kernels/l2_conv1d.py:16-222: a convolution layer with global max-pooling
@@ -877,6 +903,113 @@ class Conv1dTwoLayerKernel(KernelBase):
         is pooled from its tokens (``_pool_into``)."""
         ext.hipRBFGradRows(self._first_layer(x_unscaled, sequence_length), zrows, grows, self.radem_diag, self.chi_arr,
                            float(self.hyperparams[1]), self.fit_intercept)
+
+    # ---- derivative with respect to the INPUT, per position and channel (DESIGN.md 3.18): the second layer's input gradient
+    # pushed back through the max-pool, the ReLU and the transposed SORF of the convolution filters
+    COMPOSED_GRAD_ELEMS = ConvSORFKernel.COMPOSED_GRAD_ELEMS
+
+    def _lengths(self, input_x, sequence_length):
+        if sequence_length is None:
+            raise ValueError("sequence_length is required for convolution kernels.")
+        if input_x.shape[2] != self._xdim[2]:
+            raise RuntimeError("Unexpected input shape supplied.")
+        if isinstance(sequence_length, torch.Tensor):
+            sequence_length = sequence_length.cpu().numpy()
+        return np.ascontiguousarray(np.asarray(sequence_length).astype(np.int32, copy=False))
+
+    def first_layer_gradient(self, input_x, sequence_length, g, return_argmax=False):
+        """float64 device tensor [n, L, C]: d m / d x for any scalar m with ``g[i, f]`` = d m / d pool(x)[i, f] (float64, one
+        vector [init_rffs] for all sequences or one row per sequence) at the UNSCALED sequences ``input_x`` (dense [n, L, C] or a
+        TokenBatch).  Filter f sends g_f to the FIRST k-mer that attains its maximum, and nothing where that maximum is <= 0
+        (ReLU inactive); the windows' gradients overlap-add per position and positions past a length are exactly 0.  With
+        ``return_argmax`` also the int32 [n, init_rffs] winning k-mers (-1: inactive).  One HIP kernel where
+        ``ext.conv_maxpool_input_grad_ok`` / ``ext.conv_token_maxpool_input_grad_ok`` hold; tokens over a larger table are
+        expanded slice by slice; windows beyond 1024 elements, or a device without HIP, take ``first_layer_gradient_composed``."""
+        xin = self._private_f32(input_x)
+        lengths = self._lengths(xin, sequence_length)
+        n, L, C = xin.shape
+        gw = g if isinstance(g, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(g))
+        gw = gw.to(self.device, torch.float64)
+        if gw.dim() not in (1, 2) or (gw.dim() == 2 and gw.shape[0] != n) or gw.shape[-1] < self.init_rffs:
+            raise RuntimeError("g must be one vector of init_rffs values, or one such row per sequence.")
+        if gw.dim() == 1 or gw.stride(1) != 1:
+            gw = gw.contiguous()
+        out = torch.empty((n, L, C), dtype=torch.float64, device=self.device)
+        argmax = torch.empty((n, self.init_rffs), dtype=torch.int32, device=self.device)
+        on_hip = torch.device(self.device).type == "cuda"
+        width = self.conv_width * C
+        if isinstance(xin, TokenBatch):
+            if (on_hip and xin.is_cuda and xin.tokens.is_contiguous()
+                    and ext.conv_token_maxpool_input_grad_ok(width, xin.table.shape[0], C) == 1):
+                ext.hipConvTokenMaxpoolInputGrad(xin.tokens, xin.table, gw, out, argmax, self.radem_diag1, self.chi_arr1, lengths,
+                                                 self.conv_width)
+            else:
+                for lo in range(0, n, ConvSORFKernel.CACHE_BUILD_ROWS):
+                    hi = min(lo + ConvSORFKernel.CACHE_BUILD_ROWS, n)
+                    self._dense_first_layer_gradient(xin[lo:hi].dense().contiguous(), lengths[lo:hi],
+                                                     gw if gw.dim() == 1 else gw[lo:hi], out[lo:hi], argmax[lo:hi], on_hip)
+        else:
+            self._dense_first_layer_gradient(xin, lengths, gw, out, argmax, on_hip)
+        return (out, argmax) if return_argmax else out
+
+    def _dense_first_layer_gradient(self, x, lengths, g, out, argmax, on_hip):
+        if on_hip and ext.conv_maxpool_input_grad_ok(self.conv_width * x.shape[2]) == 1:
+            ext.hipConvMaxpoolInputGrad(x, g, out, argmax, self.radem_diag1, self.chi_arr1, lengths, self.conv_width)
+        else:
+            o, a = self.first_layer_gradient_composed(x, lengths, g)
+            out.copy_(o)
+            argmax.copy_(a)
+
+    def first_layer_gradient_composed(self, x, lengths, g):
+        """(gradient [n, L, C] float64, argmax [n, init_rffs] int32) by the unfold route, at every window width, from existing
+        operators: a bounded slice of sequences is unfolded into one-k-mer "sequences", ``hipConv1dMaxpool`` writes their ReLU'd
+        projections into zero-filled rows, the first-index argmax over a sequence's k-mers masks g (.) chi, the rows go through
+        ``transposed_sorf_rows`` and are folded back with conv_width slice additions in float64, window offset 0 first.
+        ``x`` dense float32 [n, L, C], unscaled; ``lengths`` int32 on the host; ``g`` float64, one vector or one row each."""
+        n, L, C = x.shape
+        cw, F = self.conv_width, self.init_rffs
+        d, nkmax = cw * C, L - cw + 1
+        if int(lengths.min()) < cw or int(lengths.max()) > L:
+            raise RuntimeError("All sequence lengths must be >= conv width and < array size.")
+        p = padded_dims(d)
+        R = self.radem_diag1.shape[2]
+        nk = torch.from_numpy(lengths.astype(np.int64) - (cw - 1)).to(self.device)
+        live = torch.arange(nkmax, device=self.device)[None, :] < nk[:, None]             # [n, nkmax]: window j is a k-mer
+        chi = self.chi_arr1.to(torch.float64)
+        out = torch.zeros((n, L, C), dtype=torch.float64, device=self.device)
+        argmax = torch.empty((n, F), dtype=torch.int32, device=self.device)
+        one_kmer = np.full(nkmax, cw, dtype=np.int32)
+        step = max(1, self.COMPOSED_GRAD_ELEMS // (nkmax * max(R, F)))
+        for lo in range(0, n, step):
+            hi = min(lo + step, n)
+            m = hi - lo
+            wins = x[lo:hi].unfold(1, cw, 1).permute(0, 1, 3, 2).reshape(m * nkmax, cw, C).contiguous()
+            proj = torch.zeros((m * nkmax, F), dtype=torch.float32, device=self.device)
+            ext.hipConv1dMaxpool(wins, proj, self.radem_diag1, self.chi_arr1, np.tile(one_kmer, m), cw)
+            proj = proj.view(m, nkmax, F) * live[lo:hi, :, None]                         # max(0, p_j) at the k-mers, 0 past them
+            best, at = proj.max(dim=1)
+            at = torch.argmax((proj == best[:, None, :]).to(torch.uint8), dim=1)          # the FIRST k-mer that attains it
+            at = torch.where(best > 0, at, torch.full_like(at, -1))
+            argmax[lo:hi] = at.to(torch.int32)
+            gc = (g[None, :F] if g.dim() == 1 else g[lo:hi, :F]) * chi[None, :]
+            hit = at[:, None, :] == torch.arange(nkmax, device=self.device)[None, :, None]
+            t = torch.zeros((m, nkmax, R), dtype=torch.float64, device=self.device)
+            t[:, :, :F] = torch.where(hit, gc[:, None, :].expand(m, nkmax, F), torch.zeros((), dtype=torch.float64, device=self.device))
+            gw = transposed_sorf_rows(t.view(m * nkmax, R), self.radem_diag1, p)[:, :d].reshape(m, nkmax, cw, C)
+            for q in range(cw):
+                out[lo:hi, q:q + nkmax, :] += gw[:, :, q, :]
+        out *= (torch.arange(L, device=self.device)[None, :] < torch.from_numpy(lengths).to(self.device)[:, None])[:, :, None]
+        return out, argmax
+
+    def input_gradient(self, input_x, sequence_length, weights, w_cols=None, pooled=None):
+        """float64 device tensor [n, L, C]: d/dx of ``transform_x(x, sequence_length) @ weights`` at every position and channel of
+        the UNSCALED sequences (dense or a TokenBatch); same signature and conventions as ``ConvSORFKernel.input_gradient``.
+        The sequences are pooled once (or ``pooled`` = ``pool(input_x, sequence_length)`` is taken as given), the second layer's
+        ``input_gradient`` of the pooled rows -- it carries sigma -- is the g of ``first_layer_gradient``."""
+        if pooled is None:
+            pooled = self.pool(input_x, sequence_length)
+        g = self.second_layer().input_gradient(pooled, weights, w_cols)
+        return self.first_layer_gradient(input_x, sequence_length, g)
 
     # the resident float32 cache holds complete feature rows, as for the other sequence kernels
     def cache_ok(self):

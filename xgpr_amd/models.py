@@ -18,7 +18,7 @@ from .cg import cg_fit_lib_internal, refuse_half_cache
 from .classification import fit_classifier, predict_proba
 from .exact import calc_weights_exact, calc_variance_exact
 from .dataset import TokenBatch, token_batch
-from .kernels import ConvSORFKernel, SORFKernel, make_kernel
+from .kernels import Conv1dTwoLayerKernel, ConvSORFKernel, LinearKernel, SORFKernel, make_kernel
 from .preconditioner import RandNysPreconditioner, autoselect_preconditioner
 from .crude_tuning import tune_hyperparams_crude as _tune_crude
 from .tuning import default_bounds as _default_bounds, tune_hyperparams as _tune
@@ -169,23 +169,31 @@ class xGPRegression(_ModelBase):
         var[var < 0] = 0
         return preds, var * self.trainy_std ** 2
 
-    def predict_gradient(self, input_x, get_var=False, chunk_size=2000, sequence_lengths=None, token_table=None):
+    def predict_gradient(self, input_x, get_var=False, chunk_size=2000, sequence_lengths=None, token_table=None,
+                         subgradient=False):
         """The derivative of ``predict`` with respect to the input (no counterpart in the reference) -> numpy d mean / d x; with
         ``get_var`` also d variance / d x, of the same shape.  Fixed-vector kernels RBF / Matern / Cauchy: [N, d] (DESIGN.md
         3.16).  Sequence and graph kernels (Conv1d*, Graph*), which need ``sequence_lengths``: [N, L, C], one value per position
         and channel, exactly 0 past a sequence's length; ``input_x`` may be a TokenBatch, or with ``token_table`` an integer token
         array [N, L] -- the result is then the saliency map over the table's channels.  With random features the
-        derivative is exact (the transposed SORF applied to the weighted sine / cosine terms).
+        derivative is exact (the transposed SORF applied to the weighted sine / cosine terms).  Linear: the weights themselves, [N, d].
+        Conv1dTwoLayer is not differentiable where two k-mers tie for a filter's maximum or that maximum is 0: what exists there
+        is a SUBGRADIENT under a fixed convention -- a filter's gradient goes to the first k-mer that attains its maximum, and
+        nowhere if that maximum is not positive (DESIGN.md 3.18) -- and the caller asks for it by name, ``subgradient=True``;
+        without it the two-layer kernel is refused as before.  The flag changes nothing for the other kernels.
         The variance gradient is that of the UNCLIPPED expression lambda^2 + lambda^2 z_v^T V z_v: where ``predict``
         clips a negative variance to zero, the gradient returned here is still that of the expression."""
         if self.weights is None:
             raise RuntimeError("Model has not yet been successfully fitted.")
         if get_var and self.var is None:
             raise RuntimeError("Variance was requested but suppress_var was selected when fitting.")
-        seq = type(self.kernel) is ConvSORFKernel
-        if type(self.kernel) is not SORFKernel and not seq:
-            raise RuntimeError("predict_gradient is available for the fixed-vector kernels RBF, Matern and Cauchy and for the "
-                               f"sequence and graph kernels Conv1d* / Graph* only (this model's kernel is '{self.kernel_choice}').")
+        two_layer, linear = type(self.kernel) is Conv1dTwoLayerKernel, type(self.kernel) is LinearKernel
+        seq = type(self.kernel) is ConvSORFKernel or two_layer
+        if (type(self.kernel) is not SORFKernel and not seq and not linear) or (two_layer and not subgradient):
+            raise RuntimeError("predict_gradient is available for the fixed-vector kernels RBF, Matern and Cauchy, for Linear, for the "
+                               "sequence and graph kernels Conv1d* / Graph*, and with subgradient=True for Conv1dTwoLayer (the "
+                               "max-pool's first-window convention); MiniARD is not supported "
+                               f"(this model's kernel is '{self.kernel_choice}').")
         if seq and sequence_lengths is None:
             raise RuntimeError("sequence_lengths is required for the sequence and graph kernels.")
         input_x = self._to_device(token_input(input_x, token_table, self.device) if seq else input_x)
@@ -194,13 +202,21 @@ class xGPRegression(_ModelBase):
         for i in range(0, input_x.shape[0], chunk_size):
             chunk = input_x[i:i + chunk_size]
             sl = (np.asarray(sequence_lengths[i:i + chunk_size]),) if seq else ()
-            gmean.append(self.kernel.input_gradient(chunk, *sl, self.weights))
+            if two_layer:                        # one pooling per chunk: the second layer's features and gradients read it
+                pooled = self.kernel.pool(chunk, *sl)
+                extra, features = {"pooled": pooled}, lambda: self.kernel.second_layer().transform_x(pooled)
+            else:
+                extra, features = {}, lambda: self.kernel.transform_x(chunk, *sl)
+            gmean.append(self.kernel.input_gradient(chunk, *sl, self.weights, **extra))
             if get_var:
                 nvar = self.var.shape[0]
-                xv = self.kernel.transform_x(chunk, *sl)[:, :nvar]
-                wv = torch.zeros((xv.shape[0], nvar + (nvar & 1)), dtype=torch.float64, device=xv.device)
-                wv[:, :nvar] = 2.0 * lambda_ ** 2 * (xv @ self.var)
-                gvar.append(self.kernel.input_gradient(chunk, *sl, wv, w_cols=wv.shape[1]))
+                xv = features()[:, :nvar]
+                if linear:
+                    wv = 2.0 * lambda_ ** 2 * (xv @ self.var)
+                else:
+                    wv = torch.zeros((xv.shape[0], nvar + (nvar & 1)), dtype=torch.float64, device=xv.device)
+                    wv[:, :nvar] = 2.0 * lambda_ ** 2 * (xv @ self.var)
+                gvar.append(self.kernel.input_gradient(chunk, *sl, wv, w_cols=wv.shape[1], **extra))
         gmean = torch.cat(gmean).cpu().numpy() * self.trainy_std
         if not get_var:
             return gmean

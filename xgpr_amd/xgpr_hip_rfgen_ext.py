@@ -1047,6 +1047,71 @@ def hipConvTokenInputGrad(tokens, table, weights, out, radem, chi, seqlen, sigma
         int(scaling_type), int(bool(fit_intercept)), wp, wn, _stream()))
 
 
+def conv_maxpool_input_grad_ok(width):
+    """Whether hipConvMaxpoolInputGrad's kernel serves a window of ``width`` = conv_width * C elements (padded width up to 1024)."""
+    return int(_LIB.xgpr_conv_maxpool_input_grad_ok(int(width)))
+
+
+def conv_token_maxpool_input_grad_ok(width, vocab, C):
+    """Whether hipConvTokenMaxpoolInputGrad serves the window and holds a table of ``vocab`` rows and ``C`` columns in LDS."""
+    return int(_LIB.xgpr_conv_token_maxpool_input_grad_ok(int(width), int(vocab), int(C)))
+
+
+def _pool_grad_tail(g, out, argmax, shape, chi, radem, workspace, device):
+    n = shape[0]
+    if tuple(out.shape) != tuple(shape) or tuple(argmax.shape) != (n, chi.shape[0]):
+        raise RuntimeError("Wrong array sizes.")
+    stride, avail = _grad_weights(g, n)
+    if avail < chi.shape[0]:
+        raise RuntimeError("Wrong array sizes.")
+    if workspace is None:
+        ws, wp, wn = _workspace(_LIB.xgpr_rbf_workspace_bytes(radem.shape[2]), device)
+    else:
+        ws, wp, wn = workspace, C.c_void_p(workspace.data_ptr()), C.c_size_t(workspace.numel() * workspace.element_size())
+    return stride, ws, wp, wn
+
+
+def hipConvMaxpoolInputGrad(x, g, out, argmax, radem, chi, seqlen, conv_width, workspace=None):
+    """``out[n, L, C]`` (float64, OVERWRITTEN; exactly 0.0 past a sequence's length) <- d m / d x through the first layer of the
+    two-layer kernel, for ``g[i, f]`` = d m / d (hipConv1dMaxpool's pooled value f of sequence i)
+    (include/xgpr_hip_pool_input_grad.h).  ``x`` [n, L, C] float32 UNSCALED; ``g`` float64, one vector [>= F] for all sequences or
+    [n, stride >= F]; ``argmax`` int32 [n, F] (OVERWRITTEN): the first k-mer that attains each filter's maximum, -1 where the
+    maximum is <= 0; ``seqlen`` int32 on the host."""
+    xp = _dev(x, "x", torch.float32, 3)
+    o = _dev(out, "out", torch.float64, 3)
+    am = _dev(argmax, "argmax", torch.int32, 2)
+    r = _radem3(radem)
+    c = _dev(chi, "chi", torch.float32, 1)
+    n, L, ch = x.shape
+    host, dev = _seqlens(seqlen, x.device)
+    if host.shape[0] != n:
+        raise RuntimeError("wrong array sizes")
+    stride, ws, wp, wn = _pool_grad_tail(g, out, argmax, (n, L, ch), chi, radem, workspace, x.device)
+    return _lib.check(_LIB.xgpr_conv_maxpool_input_grad_f32(
+        xp, C.c_void_p(g.data_ptr()), o, am, r, c, C.c_void_p(host.ctypes.data), C.c_void_p(dev.data_ptr()), n, L, ch, stride,
+        chi.shape[0], radem.shape[2], int(conv_width), wp, wn, _stream()))
+
+
+def hipConvTokenMaxpoolInputGrad(tokens, table, g, out, argmax, radem, chi, seqlen, conv_width, workspace=None):
+    """hipConvMaxpoolInputGrad for sequences given as tokens: ``tokens`` [n, L] uint8 index the rows of ``table`` [V, C] float32
+    (unscaled); ``out`` and ``argmax`` receive exactly what hipConvMaxpoolInputGrad writes for ``table[tokens]``.  Shapes for which
+    ``conv_token_maxpool_input_grad_ok`` is 0 raise RuntimeError and launch nothing."""
+    t = _dev(tokens, "tokens", torch.uint8, 2)
+    tab = _dev(table, "table", torch.float32, 2)
+    o = _dev(out, "out", torch.float64, 3)
+    am = _dev(argmax, "argmax", torch.int32, 2)
+    r = _radem3(radem)
+    c = _dev(chi, "chi", torch.float32, 1)
+    n, L = tokens.shape
+    host, dev = _seqlens(seqlen, tokens.device)
+    if host.shape[0] != n:
+        raise RuntimeError("wrong array sizes")
+    stride, ws, wp, wn = _pool_grad_tail(g, out, argmax, (n, L, table.shape[1]), chi, radem, workspace, tokens.device)
+    return _lib.check(_LIB.xgpr_conv_token_maxpool_input_grad_f32(
+        t, tab, C.c_void_p(g.data_ptr()), o, am, r, c, C.c_void_p(host.ctypes.data), C.c_void_p(dev.data_ptr()), n, L,
+        table.shape[0], table.shape[1], stride, chi.shape[0], radem.shape[2], int(conv_width), wp, wn, _stream()))
+
+
 def selftest_lane_xor(device="cuda"):
     """Runs the cross-lane butterfly self test; returns an int32 [6, 16, 64] CPU array."""
     out = torch.zeros(6 * 16 * 64, dtype=torch.int32, device=device)
