@@ -117,6 +117,14 @@ POOL_INPUT_GRAD_SIGNATURES = {
     "xgpr_conv_token_maxpool_input_grad_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _l, _l, _l, _l, _l, _l, _l, _i, _vp,
                                                _sz, _vp],
 }
+# ... and include/xgpr_hip_cluster.h, the sixth (tests/test_cluster_host.py); its two *_workspace_bytes functions return size_t
+CLUSTER_SIGNATURES = {
+    "xgpr_kmeans_ok": [_l, _l],
+    "xgpr_kmeans_assign_workspace_bytes": [_l, _l, _l],
+    "xgpr_kmeans_assign_f32": [_vp, _vp, _vp, _vp, _l, _l, _l, _vp, _sz, _vp],
+    "xgpr_kmeans_update_workspace_bytes": [_l, _l, _l],
+    "xgpr_kmeans_update_f32": [_vp, _vp, _vp, _vp, _l, _l, _l, _i, _vp, _sz, _vp],
+}
 STRING_FUNCS = ["xgpr_last_error", "xgpr_build_arch", "xgpr_build_id"]
 
 _lib = None
@@ -136,10 +144,10 @@ def load():
             "(run `python xgpr_amd/build.py`); xgpr_amd has no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
     for name, args in (list(SIGNATURES.items()) + list(POOL_SIGNATURES.items()) + list(INPUT_GRAD_SIGNATURES.items())
-                       + list(SEQ_INPUT_GRAD_SIGNATURES.items()) + list(POOL_INPUT_GRAD_SIGNATURES.items())):
+                       + list(SEQ_INPUT_GRAD_SIGNATURES.items()) + list(POOL_INPUT_GRAD_SIGNATURES.items()) + list(CLUSTER_SIGNATURES.items())):
         fn = getattr(lib, name)
         fn.argtypes = args
-        fn.restype = C.c_int
+        fn.restype = C.c_size_t if name in CLUSTER_SIGNATURES and name.endswith("_workspace_bytes") else C.c_int
     for name, args in SIZE_FUNCS.items():
         fn = getattr(lib, name)
         fn.argtypes = args

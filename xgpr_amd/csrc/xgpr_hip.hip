@@ -49,6 +49,7 @@ typedef enum { ncclFloat64 = 8 } ncclDataType_t;
 #include "../../include/xgpr_hip_input_grad.h"
 #include "../../include/xgpr_hip_seq_input_grad.h"
 #include "../../include/xgpr_hip_pool_input_grad.h"
+#include "../../include/xgpr_hip_cluster.h"
 
 namespace {
 
@@ -70,6 +71,7 @@ namespace {
 #include "input_grad.inc"
 #include "seq_input_grad.inc"
 #include "pool_input_grad.inc"
+#include "cluster.inc"
 
 }  // namespace
 
@@ -564,6 +566,19 @@ int xgpr_conv_token_maxpool_input_grad_f32(const uint8_t *tokens, const float *t
                                            void *stream) {
     return pool_input_grad_impl(tokens, true, table, g, out, argmax, radem, chi, seqlen_host, seqlen_dev, n, L, vocab, C, g_row_stride,
                                 num_freqs, radem_shape2, conv_width, workspace, workspace_bytes, stream);
+}
+
+// ---- include/xgpr_hip_cluster.h
+int xgpr_kmeans_ok(long num_rffs, long k) { return kmeans_ok_impl(num_rffs, k); }
+size_t xgpr_kmeans_assign_workspace_bytes(long n, long num_rffs, long k) { return kmeans_assign_workspace_bytes_impl(n, num_rffs, k); }
+int xgpr_kmeans_assign_f32(const float *rows, const double *centers, int32_t *labels, double *dist2, long n, long num_rffs, long k,
+                           void *workspace, size_t workspace_bytes, void *stream) {
+    return kmeans_assign_impl(rows, centers, labels, dist2, n, num_rffs, k, workspace, workspace_bytes, stream);
+}
+size_t xgpr_kmeans_update_workspace_bytes(long n, long num_rffs, long k) { return kmeans_update_workspace_bytes_impl(n, num_rffs, k); }
+int xgpr_kmeans_update_f32(const float *rows, const int32_t *labels, double *sums, long long *counts, long n, long num_rffs, long k,
+                           int accumulate, void *workspace, size_t workspace_bytes, void *stream) {
+    return kmeans_update_impl(rows, labels, sums, counts, n, num_rffs, k, accumulate, workspace, workspace_bytes, stream);
 }
 
 int xgpr_selftest_lane_xor(int32_t *out, void *stream) {

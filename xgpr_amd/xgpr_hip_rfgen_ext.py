@@ -1112,6 +1112,52 @@ def hipConvTokenMaxpoolInputGrad(tokens, table, g, out, argmax, radem, chi, seql
         table.shape[0], table.shape[1], stride, chi.shape[0], radem.shape[2], int(conv_width), wp, wn, _stream()))
 
 
+def kmeans_ok(num_rffs, k):
+    """Whether hipKMeansAssign / hipKMeansUpdate serve ``k`` centres over rows of ``num_rffs`` columns (a multiple of 4, at
+    most 256 centres)."""
+    return int(_LIB.xgpr_kmeans_ok(int(num_rffs), int(k)))
+
+
+def _kmeans_ws(need, workspace, device):
+    if workspace is None:
+        return _workspace(need, device) if need else (None, None, C.c_size_t(0))
+    return workspace, C.c_void_p(workspace.data_ptr()), C.c_size_t(workspace.numel() * workspace.element_size())
+
+
+def hipKMeansAssign(rows, centers, labels, dist2=None, workspace=None):
+    """``labels[i]`` (int32 [n], OVERWRITTEN) <- the lowest k that minimises ``|c_k|^2 - 2 rows[i] . c_k`` over the centres
+    ``centers`` [K, num_rffs] float64, for float32 rows taken as they are (include/xgpr_hip_cluster.h); ``dist2`` (float64 [n],
+    optional, OVERWRITTEN) <- the squared distance to that centre.  Float64 products and sums on the matrix cores, a fixed
+    order.  Shapes for which ``kmeans_ok`` is 0 raise RuntimeError and launch nothing."""
+    z = _dev(rows, "rows", torch.float32, 2)
+    c = _dev(centers, "centers", torch.float64, 2)
+    lab = _dev(labels, "labels", torch.int32, 1)
+    d = None if dist2 is None else _dev(dist2, "dist2", torch.float64, 1)
+    n, m = rows.shape
+    k = centers.shape[0]
+    if centers.shape[1] != m or labels.shape[0] != n or (dist2 is not None and dist2.shape[0] != n):
+        raise RuntimeError("Wrong array sizes.")
+    ws, wp, wn = _kmeans_ws(int(_LIB.xgpr_kmeans_assign_workspace_bytes(n, m, k)), workspace, rows.device)
+    return _lib.check(_LIB.xgpr_kmeans_assign_f32(z, c, lab, d, n, m, k, wp, wn, _stream()))
+
+
+def hipKMeansUpdate(rows, labels, sums, counts, accumulate=False, workspace=None):
+    """``sums[k]`` (float64 [K, num_rffs]) (+)= the sum of the float32 rows that carry label k, ``counts[k]`` (int64 [K]) (+)=
+    their number; labels outside [0, K) are skipped.  ``accumulate`` False: both arrays are OVERWRITTEN as a whole (zeros for an
+    empty cluster).  No atomics on floating-point values: a fixed order.  Shapes for which ``kmeans_ok`` is 0 raise RuntimeError
+    and launch nothing."""
+    z = _dev(rows, "rows", torch.float32, 2)
+    lab = _dev(labels, "labels", torch.int32, 1)
+    s = _dev(sums, "sums", torch.float64, 2)
+    cnt = _dev(counts, "counts", torch.int64, 1)
+    n, m = rows.shape
+    k = sums.shape[0]
+    if sums.shape[1] != m or labels.shape[0] != n or counts.shape[0] != k:
+        raise RuntimeError("Wrong array sizes.")
+    ws, wp, wn = _kmeans_ws(int(_LIB.xgpr_kmeans_update_workspace_bytes(n, m, k)), workspace, rows.device)
+    return _lib.check(_LIB.xgpr_kmeans_update_f32(z, lab, s, cnt, n, m, k, int(bool(accumulate)), wp, wn, _stream()))
+
+
 def selftest_lane_xor(device="cuda"):
     """Runs the cross-lane butterfly self test; returns an int32 [6, 16, 64] CPU array."""
     out = torch.zeros(6 * 16 * 64, dtype=torch.int32, device=device)
