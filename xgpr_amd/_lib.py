@@ -125,6 +125,11 @@ CLUSTER_SIGNATURES = {
     "xgpr_kmeans_update_workspace_bytes": [_l, _l, _l],
     "xgpr_kmeans_update_f32": [_vp, _vp, _vp, _vp, _l, _l, _l, _i, _vp, _sz, _vp],
 }
+# ... and include/xgpr_hip_subst_scan.h, the seventh (tests/test_subst_scan_host.py)
+SUBST_SCAN_SIGNATURES = {
+    "xgpr_conv_token_subst_scan_ok": [_l, _l, _l, _l],
+    "xgpr_conv_token_subst_scan_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _l, _l, _l, _l, _l, _l, _i, _i, _i, _vp, _sz, _vp],
+}
 STRING_FUNCS = ["xgpr_last_error", "xgpr_build_arch", "xgpr_build_id"]
 
 _lib = None
@@ -144,7 +149,8 @@ def load():
             "(run `python xgpr_amd/build.py`); xgpr_amd has no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
     for name, args in (list(SIGNATURES.items()) + list(POOL_SIGNATURES.items()) + list(INPUT_GRAD_SIGNATURES.items())
-                       + list(SEQ_INPUT_GRAD_SIGNATURES.items()) + list(POOL_INPUT_GRAD_SIGNATURES.items()) + list(CLUSTER_SIGNATURES.items())):
+                       + list(SEQ_INPUT_GRAD_SIGNATURES.items()) + list(POOL_INPUT_GRAD_SIGNATURES.items()) + list(CLUSTER_SIGNATURES.items())
+                       + list(SUBST_SCAN_SIGNATURES.items())):
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = C.c_size_t if name in CLUSTER_SIGNATURES and name.endswith("_workspace_bytes") else C.c_int

@@ -222,6 +222,24 @@ template <int LOG2P> struct TokenWindows {
     }
 };
 
+// SubstTokenWindows: TokenWindows with one more way to complete a fetch (the substitution scan, subst_scan.inc).  take_subst(v, q, tok)
+// is take(v) on the window whose token at position offset q is `tok`: the registers whose position offset equals q gather from table
+// row `tok`, every other register from the row of the byte it fetched.  Padded registers carry the offset 0xffff and never match.  The
+// fetched bytes are left as they are: one issue(j) serves every variant of window j.
+template <int LOG2P> struct SubstTokenWindows : TokenWindows<LOG2P> {
+    using Base = TokenWindows<LOG2P>;
+    __device__ __forceinline__ void take_subst(float (&v)[16], unsigned q, unsigned tok) const {
+        float nx[Base::N];
+        #pragma unroll
+        for (int r = 0; r < Base::N; r++) {
+            const unsigned p = Base::PACK ? this->pos[r] & 0xffffu : this->pos[r];
+            const unsigned t = p == q ? tok : this->tk[r];
+            nx[r] = *reinterpret_cast<const float *>(this->tab + (t * this->c4 + (Base::PACK ? this->pos[r] >> 16 : this->cho[r])));
+        }
+        wave_expand<LOG2P>(v, nx);
+    }
+};
+
 constexpr int conv_min_blocks(int LOG2P, int MODE) {
     return (conv_is_grad(MODE) && LOG2P >= 7) ? 1 : (conv_is_feat(MODE) && (LOG2P >= 7 || XGPR_CONV_C2_ALL)) ? 3 : 2;
 }

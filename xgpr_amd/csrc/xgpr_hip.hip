@@ -50,6 +50,7 @@ typedef enum { ncclFloat64 = 8 } ncclDataType_t;
 #include "../../include/xgpr_hip_seq_input_grad.h"
 #include "../../include/xgpr_hip_pool_input_grad.h"
 #include "../../include/xgpr_hip_cluster.h"
+#include "../../include/xgpr_hip_subst_scan.h"
 
 namespace {
 
@@ -70,6 +71,7 @@ namespace {
 #include "launchers.inc"
 #include "input_grad.inc"
 #include "seq_input_grad.inc"
+#include "subst_scan.inc"
 #include "pool_input_grad.inc"
 #include "cluster.inc"
 
@@ -579,6 +581,18 @@ size_t xgpr_kmeans_update_workspace_bytes(long n, long num_rffs, long k) { retur
 int xgpr_kmeans_update_f32(const float *rows, const int32_t *labels, double *sums, long long *counts, long n, long num_rffs, long k,
                            int accumulate, void *workspace, size_t workspace_bytes, void *stream) {
     return kmeans_update_impl(rows, labels, sums, counts, n, num_rffs, k, accumulate, workspace, workspace_bytes, stream);
+}
+
+// ---- include/xgpr_hip_subst_scan.h
+int xgpr_conv_token_subst_scan_ok(long width, long vocab, long C, long num_freqs) {
+    return conv_token_subst_scan_ok_impl(width, vocab, C, num_freqs);
+}
+int xgpr_conv_token_subst_scan_f32(const uint8_t *tokens, const float *table, const double *w, double *out, const int8_t *radem,
+                                   const float *chi, const int32_t *seqlen_host, const int32_t *seqlen_dev, long n, long L, long vocab,
+                                   long C, long num_freqs, long radem_shape2, int conv_width, int scaling_type, int fit_intercept,
+                                   void *workspace, size_t workspace_bytes, void *stream) {
+    return subst_scan_impl(tokens, table, w, out, radem, chi, seqlen_host, seqlen_dev, n, L, vocab, C, num_freqs, radem_shape2,
+                           conv_width, scaling_type, fit_intercept, workspace, workspace_bytes, stream);
 }
 
 int xgpr_selftest_lane_xor(int32_t *out, void *stream) {

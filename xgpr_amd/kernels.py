@@ -557,6 +557,85 @@ class ConvSORFKernel(KernelBase):
         out *= (torch.arange(L, device=self.device)[None, :] < torch.from_numpy(lengths).to(self.device)[:, None])[:, :, None]
         return out
 
+    # ---- the exact effect of every single-token substitution on a weighted sum of the features
+    COMPOSED_SCAN_ELEMS = 1 << 25    # float32 elements of mutant feature rows the composed route holds per slice
+
+    def _scan_inputs(self, batch, sequence_length, weights):
+        if not isinstance(batch, TokenBatch):
+            raise RuntimeError("substitution_scan needs sequences given as tokens (a TokenBatch).")
+        xs = self.scaled_f32(batch)
+        lengths = self._host_lengths(xs, sequence_length)
+        if lengths.shape[0] != xs.shape[0]:
+            raise RuntimeError("sequence_length must hold one length per sequence.")
+        w = weights if isinstance(weights, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(weights))
+        w = w.to(self.device, torch.float64).contiguous()
+        if w.dim() != 1 or w.shape[0] != self.num_rffs:
+            raise RuntimeError("weights must be one vector of num_rffs values.")
+        return xs, lengths, w
+
+    def substitution_scan(self, batch, sequence_length, weights):
+        """float64 device tensor [n, L, V]: ``transform_x(sequence with token l replaced by v) @ weights`` minus
+        ``transform_x(sequence) @ weights`` for every position l and every row v of the TokenBatch's table -- the exact effect of
+        every single substitution, not its first-order estimate (``input_gradient``).  Exactly 0 at a sequence's own token and
+        past its length.  ``weights``: one vector of num_rffs values.  A substitution at l changes only the conv_width windows
+        that cover l, so one HIP kernel transforms L V conv_width windows instead of the L V (L - conv_width + 1) of L V mutant
+        sequences, and writes no mutant (``ext.hipConvTokenSubstScan``); where ``ext.conv_token_subst_scan_ok`` is 0 (windows
+        of more than 1024 elements, a table the LDS image does not hold) or the tokens are not contiguous the result comes from
+        ``substitution_scan_composed``."""
+        xs, lengths, w = self._scan_inputs(batch, sequence_length, weights)
+        n, L, C = xs.shape
+        V = xs.table.shape[0]
+        if not (xs.is_cuda and xs.tokens.is_contiguous()
+                and ext.conv_token_subst_scan_ok(self.conv_width * C, V, C, self.num_freqs) == 1):
+            return self._scan_composed(xs, lengths, w)
+        out = torch.empty((n, L, V), dtype=torch.float64, device=self.device)
+        ext.hipConvTokenSubstScan(xs.tokens, xs.table.contiguous(), w, out, self.radem_diag, self.chi_arr, lengths, self.conv_width,
+                                  self.scaling_type, self.fit_intercept)
+        return out
+
+    def substitution_scan_composed(self, batch, sequence_length, weights):
+        """The same result from existing operators, at every window width and table size: a bounded slice of (sequence,
+        position, token) mutants is written out as token rows, ``fill_feature_rows`` makes their float32 feature rows,
+        ``hipZCacheBlockProject`` with one column their weighted sums, and the unmutated sequence's value is subtracted.  At most
+        ``COMPOSED_SCAN_ELEMS`` float32 row elements are held at a time."""
+        return self._scan_composed(*self._scan_inputs(batch, sequence_length, weights))
+
+    def _scan_composed(self, xs, lengths, w):
+        n, L, _ = xs.shape
+        V, M, dev = xs.table.shape[0], self.num_rffs, self.device
+        if n and (int(lengths.min()) < self.conv_width or int(lengths.max()) > L):
+            raise RuntimeError("All sequence lengths must be >= conv width and < array size.")
+        tokens, lens_dev = xs.tokens.contiguous(), torch.from_numpy(lengths).to(dev)
+        wcol = w.clone()
+        if self.fit_intercept:
+            wcol[0] = 0.                                 # column 0 is the constant 1 of both rows
+        wcol = wcol[:, None].contiguous()
+        step = max(1, self.COMPOSED_SCAN_ELEMS // M)
+
+        def project(tok, seq_ids):
+            rows = torch.empty((tok.shape[0], M), dtype=torch.float32, device=dev)
+            self.fill_feature_rows(TokenBatch(tok, xs.table), lengths[seq_ids.cpu().numpy()], rows)
+            val = torch.empty((tok.shape[0], 1), dtype=torch.float64, device=dev)
+            ext.hipZCacheBlockProject(rows, wcol, val, False, 1.0)
+            return val[:, 0]
+
+        base = torch.empty(n, dtype=torch.float64, device=dev)
+        for lo in range(0, n, step):
+            ids = torch.arange(lo, min(lo + step, n), device=dev)
+            base[lo:lo + step] = project(tokens[ids], ids)
+        out = torch.empty((n, L, V), dtype=torch.float64, device=dev)
+        flat = out.view(-1)
+        for lo in range(0, n * L * V, step):
+            ids = torch.arange(lo, min(lo + step, n * L * V), device=dev)
+            seq, pos, tok = ids // (L * V), (ids // V) % L, ids % V
+            mut = tokens[seq]
+            mut[torch.arange(ids.shape[0], device=dev), pos] = tok.to(torch.uint8)
+            flat[lo:lo + step] = project(mut, seq) - base[seq]
+        # the own token and the positions past a length: the mutant is the sequence itself
+        pos = torch.arange(L, device=dev)
+        same = (pos[None, :] >= lens_dev[:, None])[:, :, None] | (torch.arange(V, device=dev)[None, None, :] == tokens.long()[:, :, None])
+        return out.masked_fill_(same, 0.0)
+
     def grad_rows_ok(self):
         """Whether ``fill_grad_rows`` can write this kernel's float32 feature AND gradient rows, and the exact NMLL
         gradient's accumulations can run on them (nmll.calc_gradient_terms): a HIP device -- the writer serves every

@@ -222,6 +222,39 @@ class xGPRegression(_ModelBase):
             return gmean
         return gmean, torch.cat(gvar).cpu().numpy() * self.trainy_std ** 2
 
+    def predict_substitutions(self, input_x, sequence_lengths=None, token_table=None, chunk_size=64):
+        """The exact effect of every single substitution on ``predict`` (no counterpart in the reference) -> numpy float64
+        [N, L, V]: entry [i, l, v] is the predicted mean of sequence i with its token at position l replaced by row v of the
+        token table, minus the predicted mean of sequence i itself, in the units of y (times the training y's standard
+        deviation; the offset cancels).  Exactly 0 at a sequence's own token and past its length.  ``input_x`` is a TokenBatch,
+        or with ``token_table`` an integer token array [N, L]; ``sequence_lengths`` is required.  Available for the sequence and
+        graph kernels Conv1dRBF / Conv1dMatern / Conv1dCauchy and GraphRBF / GraphMatern / GraphCauchy, whose feature row is a
+        sum over k-mer windows: a substitution changes only the conv_width windows that cover it, so the scan costs
+        L V conv_width window transforms, not the L V (L - conv_width + 1) of L V mutant sequences, and no mutant is written
+        (``predict_gradient`` gives the first-order estimate).  ``chunk_size`` sequences go to the device at a
+        time.  The VARIANCE of the mutants is not covered: it is a quadratic form of the whole feature row and has no
+        per-window decomposition."""
+        if self.weights is None:
+            raise RuntimeError("Model has not yet been successfully fitted.")
+        if type(self.kernel) is not ConvSORFKernel:
+            raise RuntimeError("predict_substitutions is available for the sequence and graph kernels Conv1dRBF, Conv1dMatern, "
+                               "Conv1dCauchy, GraphRBF, GraphMatern and GraphCauchy on token input; Conv1dTwoLayer, the "
+                               "fixed-vector kernels, Linear and MiniARD are not supported "
+                               f"(this model's kernel is '{self.kernel_choice}').")
+        if sequence_lengths is None:
+            raise RuntimeError("sequence_lengths is required for the sequence and graph kernels.")
+        input_x = token_input(input_x, token_table, self.device)
+        if not isinstance(input_x, TokenBatch):
+            raise RuntimeError("predict_substitutions needs token input: a TokenBatch, or integer tokens [N, L] with token_table.")
+        sequence_lengths = np.asarray(sequence_lengths)
+        if sequence_lengths.shape[0] != input_x.shape[0]:
+            raise RuntimeError("The shape[0] of sequence_lengths must match the shape[0] of input_x.")
+        scans = [self.kernel.substitution_scan(input_x[i:i + chunk_size], sequence_lengths[i:i + chunk_size], self.weights)
+                 for i in range(0, input_x.shape[0], chunk_size)]
+        if not scans:
+            return np.zeros((0, input_x.shape[1], input_x.table.shape[0]))
+        return torch.cat(scans).cpu().numpy() * self.trainy_std
+
     def exact_nmll(self, hyperparams, dataset):
         self.set_hyperparams(hyperparams, dataset)
         return _nmll.exact_nmll(*self._solver_pair(dataset))

@@ -1047,6 +1047,40 @@ def hipConvTokenInputGrad(tokens, table, weights, out, radem, chi, seqlen, sigma
         int(scaling_type), int(bool(fit_intercept)), wp, wn, _stream()))
 
 
+def conv_token_subst_scan_ok(width, vocab, C, num_freqs):
+    """Whether hipConvTokenSubstScan's kernel serves a window of ``width`` = conv_width * C elements over a table of ``vocab``
+    rows and ``C`` columns (padded width up to 1024, a table the LDS image holds); no device work."""
+    return int(_LIB.xgpr_conv_token_subst_scan_ok(int(width), int(vocab), int(C), int(num_freqs)))
+
+
+def hipConvTokenSubstScan(tokens, table, weights, out, radem, chi, seqlen, conv_width, scaling_type, fit_intercept, workspace=None):
+    """``out[n, L, V]`` (float64, OVERWRITTEN) <- ``features(sequence with token l replaced by v) @ weights`` minus
+    ``features(sequence) @ weights`` for every position l and token v of the sequence and graph kernels
+    (include/xgpr_hip_subst_scan.h): exactly +0.0 at a sequence's own token and past its length.  ``tokens`` [n, L] uint8 index
+    the rows of ``table`` [V, C] float32 (already sigma-scaled); ``weights`` float64 [2 * num_freqs], one vector for all
+    sequences (``weights[0]`` is ignored under fit_intercept); ``seqlen`` int32 on the host.  Shapes for which
+    ``conv_token_subst_scan_ok`` is 0 raise RuntimeError and launch nothing."""
+    t = _dev(tokens, "tokens", torch.uint8, 2)
+    tab = _dev(table, "table", torch.float32, 2)
+    w = _dev(weights, "weights", torch.float64, 1)
+    g = _dev(out, "out", torch.float64, 3)
+    r = _radem3(radem)
+    c = _dev(chi, "chi", torch.float32, 1)
+    n, L = tokens.shape
+    if tuple(out.shape) != (n, L, table.shape[0]) or weights.shape[0] != 2 * chi.shape[0]:
+        raise RuntimeError("Wrong array sizes.")
+    host, dev = _seqlens(seqlen, tokens.device)
+    if host.shape[0] != n:
+        raise RuntimeError("wrong array sizes")
+    if workspace is None:
+        ws, wp, wn = _workspace(_LIB.xgpr_rbf_workspace_bytes(radem.shape[2]), tokens.device)
+    else:
+        ws, wp, wn = workspace, C.c_void_p(workspace.data_ptr()), C.c_size_t(workspace.numel() * workspace.element_size())
+    return _lib.check(_LIB.xgpr_conv_token_subst_scan_f32(
+        t, tab, w, g, r, c, C.c_void_p(host.ctypes.data), C.c_void_p(dev.data_ptr()), n, L, table.shape[0], table.shape[1],
+        chi.shape[0], radem.shape[2], int(conv_width), int(scaling_type), int(bool(fit_intercept)), wp, wn, _stream()))
+
+
 def conv_maxpool_input_grad_ok(width):
     """Whether hipConvMaxpoolInputGrad's kernel serves a window of ``width`` = conv_width * C elements (padded width up to 1024)."""
     return int(_LIB.xgpr_conv_maxpool_input_grad_ok(int(width)))
