@@ -240,6 +240,34 @@ template <int LOG2P> struct SubstTokenWindows : TokenWindows<LOG2P> {
     }
 };
 
+// IndelTokenWindows: the windows of a sequence with ONE token deleted or inserted (the indel scan, indel_scan.inc), fetched from the
+// original bytes by remapping each register's position offset -- no mutant is written.  Window jm of the mutant starts at the original
+// byte jm, and q is the edit's position offset inside it.
+//   issue_del(jm, q)   offset k reads the original k + (k >= q): the tokens before the deleted one, then those after it.  The range
+//                      is the conv_width + 1 original bytes that can be touched; padded registers (offset 0xffff) stay outside it.
+//   issue_ins(jm, q)   offset k < q reads k, k > q reads k - 1; the register at k == q fetches a byte that take_subst(v, q, tok)
+//                      (SubstTokenWindows) replaces by the inserted token.  Only conv_width - 1 original bytes belong to such a window and
+//                      the range is set to them: the byte behind an appended token, which may lie past the array, is never addressed.
+template <int LOG2P> struct IndelTokenWindows : SubstTokenWindows<LOG2P> {
+    using Base = TokenWindows<LOG2P>;
+    __device__ __forceinline__ void issue_del(int jm, unsigned q) {
+        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(this->trow + jm), 0, this->cw + 1, 0x00020000);
+        #pragma unroll
+        for (int r = 0; r < Base::N; r++) {
+            const unsigned k = Base::PACK ? this->pos[r] & 0xffffu : this->pos[r];
+            this->tk[r] = __builtin_amdgcn_raw_buffer_load_b8(rs, (int)(k + (k >= q ? 1u : 0u)), 0, 0);
+        }
+    }
+    __device__ __forceinline__ void issue_ins(int jm, unsigned q) {
+        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(this->trow + jm), 0, this->cw - 1, 0x00020000);
+        #pragma unroll
+        for (int r = 0; r < Base::N; r++) {
+            const unsigned k = Base::PACK ? this->pos[r] & 0xffffu : this->pos[r];
+            this->tk[r] = __builtin_amdgcn_raw_buffer_load_b8(rs, (int)(k - (k > q ? 1u : 0u)), 0, 0);
+        }
+    }
+};
+
 constexpr int conv_min_blocks(int LOG2P, int MODE) {
     return (conv_is_grad(MODE) && LOG2P >= 7) ? 1 : (conv_is_feat(MODE) && (LOG2P >= 7 || XGPR_CONV_C2_ALL)) ? 3 : 2;
 }

@@ -51,6 +51,7 @@ typedef enum { ncclFloat64 = 8 } ncclDataType_t;
 #include "../../include/xgpr_hip_pool_input_grad.h"
 #include "../../include/xgpr_hip_cluster.h"
 #include "../../include/xgpr_hip_subst_scan.h"
+#include "../../include/xgpr_hip_indel_scan.h"
 
 namespace {
 
@@ -72,6 +73,7 @@ namespace {
 #include "input_grad.inc"
 #include "seq_input_grad.inc"
 #include "subst_scan.inc"
+#include "indel_scan.inc"
 #include "pool_input_grad.inc"
 #include "cluster.inc"
 
@@ -593,6 +595,26 @@ int xgpr_conv_token_subst_scan_f32(const uint8_t *tokens, const float *table, co
                                    void *workspace, size_t workspace_bytes, void *stream) {
     return subst_scan_impl(tokens, table, w, out, radem, chi, seqlen_host, seqlen_dev, n, L, vocab, C, num_freqs, radem_shape2,
                            conv_width, scaling_type, fit_intercept, workspace, workspace_bytes, stream);
+}
+
+// ---- include/xgpr_hip_indel_scan.h
+int xgpr_conv_token_indel_scan_ok(long width, long vocab, long C, long num_freqs) {
+    return conv_token_indel_scan_ok_impl(width, vocab, C, num_freqs);
+}
+int xgpr_conv_token_window_scores_f32(const uint8_t *tokens, const float *table, const double *w, double *scores, const int8_t *radem,
+                                      const float *chi, const int32_t *seqlen_host, const int32_t *seqlen_dev, long n, long L, long vocab,
+                                      long C, long num_freqs, long radem_shape2, int conv_width, int fit_intercept, void *workspace,
+                                      size_t workspace_bytes, void *stream) {
+    return window_scores_impl(tokens, table, w, scores, radem, chi, seqlen_host, seqlen_dev, n, L, vocab, C, num_freqs, radem_shape2,
+                              conv_width, fit_intercept, workspace, workspace_bytes, stream);
+}
+int xgpr_conv_token_indel_scan_f32(const uint8_t *tokens, const float *table, const double *w, const double *scores, double *del,
+                                   double *ins, const int8_t *radem, const float *chi, const int32_t *seqlen_host,
+                                   const int32_t *seqlen_dev, long n, long L, long vocab, long C, long num_freqs, long radem_shape2,
+                                   int conv_width, int scaling_type, int fit_intercept, void *workspace, size_t workspace_bytes,
+                                   void *stream) {
+    return indel_scan_impl(tokens, table, w, scores, del, ins, radem, chi, seqlen_host, seqlen_dev, n, L, vocab, C, num_freqs,
+                           radem_shape2, conv_width, scaling_type, fit_intercept, workspace, workspace_bytes, stream);
 }
 
 int xgpr_selftest_lane_xor(int32_t *out, void *stream) {

@@ -636,6 +636,133 @@ class ConvSORFKernel(KernelBase):
         same = (pos[None, :] >= lens_dev[:, None])[:, :, None] | (torch.arange(V, device=dev)[None, None, :] == tokens.long()[:, :, None])
         return out.masked_fill_(same, 0.0)
 
+    # ---- the exact effect of every single-token deletion and insertion on a weighted sum of the features
+    def _indel_operator_ok(self, xs):
+        return bool(xs.is_cuda and xs.tokens.is_contiguous()
+                    and ext.conv_token_indel_scan_ok(self.conv_width * xs.shape[2], xs.table.shape[0], xs.shape[2], self.num_freqs) == 1)
+
+    def window_scores(self, batch, sequence_length, weights):
+        """float64 device tensor [n, L]: the share of every k-mer window in ``transform_x(sequence) @ weights`` before the k-mer
+        normaliser -- ``scores[i, j] = sum_f (w[2f] cos p_f + w[2f+1] sin p_f)`` over the projections p of window j
+        (``weights[0]`` dropped under the intercept), exactly 0 for j >= nk = length - conv_width + 1.
+        ``sqrt(1 / num_freqs) / {1, sqrt(nk), nk} * scores[i].sum()`` plus ``weights[0]`` under the intercept is
+        ``transform_x(sequence i) @ weights``.  One HIP kernel (``ext.hipConvTokenWindowScores``) where
+        ``ext.conv_token_indel_scan_ok`` holds; elsewhere every window goes through ``fill_feature_rows`` as a sequence of its own."""
+        xs, lengths, w = self._scan_inputs(batch, sequence_length, weights)
+        if not self._indel_operator_ok(xs):
+            return self._window_scores_composed(xs, lengths, w)
+        scores = torch.empty(xs.shape[:2], dtype=torch.float64, device=self.device)
+        ext.hipConvTokenWindowScores(xs.tokens, xs.table.contiguous(), w, scores, self.radem_diag, self.chi_arr, lengths, self.conv_width,
+                                     self.fit_intercept)
+        return scores
+
+    def indel_scan(self, batch, sequence_length, weights):
+        """(deletions [n, L], insertions [n, L + 1, V]), float64 device tensors: ``transform_x(mutant) @ weights`` minus
+        ``transform_x(sequence) @ weights`` for the sequence without its token at position p, and for the sequence with row v of the
+        TokenBatch's table inserted before position g (g = length appends) -- exact.  Exactly 0 for p >= length and g > length;
+        the deletions of a sequence of exactly conv_width tokens (no window left) are NaN.  An indel only shifts the windows that
+        do not touch the edit site, so the HIP kernels (``ext.hipConvTokenWindowScores`` + ``ext.hipConvTokenIndelScan``)
+        transform about conv_width windows per edit and the nk windows of the sequence once, rescale the total by the new
+        k-mer normaliser, and write no mutant; where ``ext.conv_token_indel_scan_ok`` is 0 or the tokens are not contiguous the
+        result comes from ``indel_scan_composed``."""
+        xs, lengths, w = self._scan_inputs(batch, sequence_length, weights)
+        if not self._indel_operator_ok(xs):
+            return self._indel_composed(xs, lengths, w)
+        n, L, _ = xs.shape
+        table = xs.table.contiguous()
+        scores = torch.empty((n, L), dtype=torch.float64, device=self.device)
+        dele = torch.empty((n, L), dtype=torch.float64, device=self.device)
+        ins = torch.empty((n, L + 1, table.shape[0]), dtype=torch.float64, device=self.device)
+        ext.hipConvTokenWindowScores(xs.tokens, table, w, scores, self.radem_diag, self.chi_arr, lengths, self.conv_width, self.fit_intercept)
+        ext.hipConvTokenIndelScan(xs.tokens, table, w, scores, dele, ins, self.radem_diag, self.chi_arr, lengths, self.conv_width,
+                                  self.scaling_type, self.fit_intercept)
+        return dele, ins
+
+    def indel_scan_composed(self, batch, sequence_length, weights):
+        """The same result from existing operators, at every window width and table size: bounded slices of deletion and insertion
+        mutants are written out as token rows of L + 1 positions, ``fill_feature_rows`` makes their float32 feature rows,
+        ``hipZCacheBlockProject`` with one column their weighted sums, the unmutated sequence's value is subtracted, and the zeros
+        and NaNs of the contract are applied.  At most ``COMPOSED_SCAN_ELEMS`` float32 row elements are held at a time."""
+        return self._indel_composed(*self._scan_inputs(batch, sequence_length, weights))
+
+    def _projector(self, table, w):
+        """f(token rows, int32 host lengths) -> their feature rows times w (column 0 dropped under the intercept), float64 [m]."""
+        wcol = w.clone()
+        if self.fit_intercept:
+            wcol[0] = 0.                                 # column 0 is the constant 1 of every row
+        wcol = wcol[:, None].contiguous()
+
+        def project(tok, lens):
+            rows = torch.empty((tok.shape[0], self.num_rffs), dtype=torch.float32, device=self.device)
+            self.fill_feature_rows(TokenBatch(tok.contiguous(), table), lens, rows)
+            val = torch.empty((tok.shape[0], 1), dtype=torch.float64, device=self.device)
+            ext.hipZCacheBlockProject(rows, wcol, val, False, 1.0)
+            return val[:, 0]
+        return project
+
+    def _check_lengths(self, lengths, n, L):
+        if n and (int(lengths.min()) < self.conv_width or int(lengths.max()) > L):
+            raise RuntimeError("All sequence lengths must be >= conv width and < array size.")
+
+    def _window_scores_composed(self, xs, lengths, w):
+        n, L, _ = xs.shape
+        cw, dev = self.conv_width, self.device
+        self._check_lengths(lengths, n, L)
+        project = self._projector(xs.table, w)
+        wins = xs.tokens.unfold(1, cw, 1)                # [n, L - cw + 1, cw]: every window as a sequence of one window
+        nw = wins.shape[1]
+        live = torch.arange(nw, device=dev)[None, :] < (torch.from_numpy(lengths).to(dev)[:, None] - cw + 1)
+        idx = live.reshape(-1).nonzero()[:, 0]
+        flat = wins.reshape(n * nw, cw)
+        vals = torch.empty(idx.shape[0], dtype=torch.float64, device=dev)
+        step = max(1, self.COMPOSED_SCAN_ELEMS // self.num_rffs)
+        for lo in range(0, idx.shape[0], step):
+            ids = idx[lo:lo + step]
+            vals[lo:lo + step] = project(flat[ids], np.full(ids.shape[0], cw, dtype=np.int32))
+        out = torch.zeros((n, L), dtype=torch.float64, device=dev)
+        # (a row of one window is sqrt(1 / F) (cos, sin) under every averaging)
+        out[:, :nw][live] = vals / float(np.sqrt(1.0 / self.num_freqs))
+        return out
+
+    def _indel_composed(self, xs, lengths, w):
+        n, L, _ = xs.shape
+        V, cw, dev = xs.table.shape[0], self.conv_width, self.device
+        self._check_lengths(lengths, n, L)
+        project = self._projector(xs.table, w)
+        tokens, lens_dev = xs.tokens.contiguous(), torch.from_numpy(lengths).to(dev).long()
+        step = max(1, self.COMPOSED_SCAN_ELEMS // self.num_rffs)
+        k = torch.arange(L + 1, device=dev)[None, :]
+
+        base = torch.empty(n, dtype=torch.float64, device=dev)
+        for lo in range(0, n, step):
+            base[lo:lo + step] = project(tokens[lo:lo + step], lengths[lo:lo + step])
+        dele = torch.empty((n, L), dtype=torch.float64, device=dev)
+        flat = dele.view(-1)
+        for lo in range(0, n * L, step):
+            ids = torch.arange(lo, min(lo + step, n * L), device=dev)
+            seq, pos = ids // L, ids % L
+            pos = torch.where(lens_dev[seq] > cw, pos, L + 1)                   # (no mutant: the sequence itself, overwritten below)
+            src = (k + (k >= pos[:, None]).long()).clamp_(max=L - 1)            # position k of the mutant reads k + (k >= p)
+            mut = torch.gather(tokens[seq], 1, src)
+            mlen = (lens_dev[seq] - 1).clamp_(min=cw)                           # (entries with no mutant are overwritten below)
+            flat[lo:lo + step] = project(mut, mlen.to(torch.int32).cpu().numpy()) - base[seq]
+        ins = torch.empty((n, L + 1, V), dtype=torch.float64, device=dev)
+        flat = ins.view(-1)
+        for lo in range(0, n * (L + 1) * V, step):
+            ids = torch.arange(lo, min(lo + step, n * (L + 1) * V), device=dev)
+            seq, gap, tok = ids // ((L + 1) * V), (ids // V) % (L + 1), ids % V
+            src = (k - (k > gap[:, None]).long()).clamp_(max=L - 1)             # k < g reads k, k > g reads k - 1 ...
+            mut = torch.gather(tokens[seq], 1, src)
+            mut[torch.arange(ids.shape[0], device=dev), gap] = tok.to(torch.uint8)      # ... and k == g is the new token
+            mlen = lens_dev[seq] + (gap <= lens_dev[seq]).long()               # (no such gap: the sequence itself, overwritten below)
+            flat[lo:lo + step] = project(mut, mlen.to(torch.int32).cpu().numpy()) - base[seq]
+        # the contract's zeros (no such position or gap) and NaNs (a deletion that leaves no window)
+        pos = torch.arange(L, device=dev)[None, :]
+        dele.masked_fill_((lens_dev[:, None] == cw) & (pos < lens_dev[:, None]), float("nan"))
+        dele.masked_fill_(pos >= lens_dev[:, None], 0.0)
+        ins.masked_fill_((k > lens_dev[:, None])[:, :, None], 0.0)
+        return dele, ins
+
     def grad_rows_ok(self):
         """Whether ``fill_grad_rows`` can write this kernel's float32 feature AND gradient rows, and the exact NMLL
         gradient's accumulations can run on them (nmll.calc_gradient_terms): a HIP device -- the writer serves every

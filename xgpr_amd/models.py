@@ -255,6 +255,61 @@ class xGPRegression(_ModelBase):
             return np.zeros((0, input_x.shape[1], input_x.table.shape[0]))
         return torch.cat(scans).cpu().numpy() * self.trainy_std
 
+    def _token_scan_input(self, name, input_x, sequence_lengths, token_table):
+        """The refusals ``predict_substitutions`` makes, for the other position-by-position scans -> (TokenBatch, lengths)."""
+        if self.weights is None:
+            raise RuntimeError("Model has not yet been successfully fitted.")
+        if type(self.kernel) is not ConvSORFKernel:
+            raise RuntimeError(f"{name} is available for the sequence and graph kernels Conv1dRBF, Conv1dMatern, "
+                               "Conv1dCauchy, GraphRBF, GraphMatern and GraphCauchy on token input; Conv1dTwoLayer, the "
+                               "fixed-vector kernels, Linear and MiniARD are not supported "
+                               f"(this model's kernel is '{self.kernel_choice}').")
+        if sequence_lengths is None:
+            raise RuntimeError("sequence_lengths is required for the sequence and graph kernels.")
+        input_x = token_input(input_x, token_table, self.device)
+        if not isinstance(input_x, TokenBatch):
+            raise RuntimeError(f"{name} needs token input: a TokenBatch, or integer tokens [N, L] with token_table.")
+        sequence_lengths = np.asarray(sequence_lengths)
+        if sequence_lengths.shape[0] != input_x.shape[0]:
+            raise RuntimeError("The shape[0] of sequence_lengths must match the shape[0] of input_x.")
+        return input_x, sequence_lengths
+
+    def predict_indels(self, input_x, sequence_lengths=None, token_table=None, chunk_size=64):
+        """The exact effect of every single deletion and insertion on ``predict`` (no counterpart in the reference) -> numpy
+        float64 (deletions [N, L], insertions [N, L + 1, V]): deletions[i, p] is the predicted mean of sequence i without its
+        token at position p, insertions[i, g, v] that of sequence i with row v of the token table inserted before position g
+        (g = the length appends), each minus the predicted mean of sequence i itself, in the units of y (times the training
+        y's standard deviation; the offset cancels).  Exactly 0 for p >= the length and g > the length; NaN for the deletions of
+        a sequence of exactly conv_width tokens, whose mutant has no k-mer.  Input and kernels as for ``predict_substitutions``.
+        An indel only shifts the windows away from the edit, so the scan transforms about conv_width windows per edit plus
+        the sequence's own windows once, and rescales the total by the mutant's k-mer normaliser; no mutant is written
+        (DESIGN.md 3.21).  The VARIANCE of the mutants is not covered."""
+        input_x, sequence_lengths = self._token_scan_input("predict_indels", input_x, sequence_lengths, token_table)
+        scans = [self.kernel.indel_scan(input_x[i:i + chunk_size], sequence_lengths[i:i + chunk_size], self.weights)
+                 for i in range(0, input_x.shape[0], chunk_size)]
+        if not scans:
+            return np.zeros((0, input_x.shape[1])), np.zeros((0, input_x.shape[1] + 1, input_x.table.shape[0]))
+        return (torch.cat([s[0] for s in scans]).cpu().numpy() * self.trainy_std,
+                torch.cat([s[1] for s in scans]).cpu().numpy() * self.trainy_std)
+
+    def predict_window_scores(self, input_x, sequence_lengths=None, token_table=None, chunk_size=64):
+        """The share of every k-mer window in ``predict`` (no counterpart in the reference) -> numpy float64 [N, L]: entry
+        [i, j] is what window j = tokens j .. j + conv_width - 1 of sequence i adds to the predicted mean, in the units of y;
+        exactly 0 for j >= length - conv_width + 1.  A row's sum plus the training y's mean (plus ``weights[0]`` times its
+        standard deviation when the kernel fits an intercept) is ``predict``.  Input and kernels as for ``predict_indels``."""
+        input_x, sequence_lengths = self._token_scan_input("predict_window_scores", input_x, sequence_lengths, token_table)
+        k = self.kernel
+        out = []
+        for i in range(0, input_x.shape[0], chunk_size):
+            lens = sequence_lengths[i:i + chunk_size]
+            nk = torch.from_numpy(np.maximum(np.asarray(lens, dtype=np.int64) - k.conv_width + 1, 1)).to(self.device, torch.float64)
+            r = float(np.sqrt(1.0 / k.num_freqs)) / (nk if k.scaling_type == 2 else torch.sqrt(nk) if k.scaling_type == 1
+                                                     else torch.ones_like(nk))
+            out.append(r[:, None] * k.window_scores(input_x[i:i + chunk_size], lens, self.weights))
+        if not out:
+            return np.zeros((0, input_x.shape[1]))
+        return torch.cat(out).cpu().numpy() * self.trainy_std
+
     def exact_nmll(self, hyperparams, dataset):
         self.set_hyperparams(hyperparams, dataset)
         return _nmll.exact_nmll(*self._solver_pair(dataset))

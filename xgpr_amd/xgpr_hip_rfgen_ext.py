@@ -1081,6 +1081,63 @@ def hipConvTokenSubstScan(tokens, table, weights, out, radem, chi, seqlen, conv_
         chi.shape[0], radem.shape[2], int(conv_width), int(scaling_type), int(bool(fit_intercept)), wp, wn, _stream()))
 
 
+def conv_token_indel_scan_ok(width, vocab, C, num_freqs):
+    """Whether the kernels of hipConvTokenWindowScores / hipConvTokenIndelScan serve a window of ``width`` = conv_width * C elements over
+    a table of ``vocab`` rows and ``C`` columns (where ``conv_token_subst_scan_ok`` is 1); no device work."""
+    return int(_LIB.xgpr_conv_token_indel_scan_ok(int(width), int(vocab), int(C), int(num_freqs)))
+
+
+def _indel_operands(tokens, table, weights, radem, chi, seqlen, workspace):
+    ops = (_dev(tokens, "tokens", torch.uint8, 2), _dev(table, "table", torch.float32, 2), _dev(weights, "weights", torch.float64, 1),
+           _radem3(radem), _dev(chi, "chi", torch.float32, 1))
+    if weights.shape[0] != 2 * chi.shape[0]:
+        raise RuntimeError("Wrong array sizes.")
+    host, dev = _seqlens(seqlen, tokens.device)
+    if host.shape[0] != tokens.shape[0]:
+        raise RuntimeError("wrong array sizes")
+    if workspace is None:
+        ws, wp, wn = _workspace(_LIB.xgpr_rbf_workspace_bytes(radem.shape[2]), tokens.device)
+    else:
+        ws, wp, wn = workspace, C.c_void_p(workspace.data_ptr()), C.c_size_t(workspace.numel() * workspace.element_size())
+    return ops, host, dev, ws, wp, wn
+
+
+def hipConvTokenWindowScores(tokens, table, weights, scores, radem, chi, seqlen, conv_width, fit_intercept, workspace=None):
+    """``scores[n, L]`` (float64, OVERWRITTEN) <- the score of every k-mer window of the sequence and graph kernels
+    (include/xgpr_hip_indel_scan.h): ``scores[i, j] = sum_f (w[2f] cos p_f + w[2f+1] sin p_f)`` over the projections p of window j,
+    exactly +0.0 for j >= nk.  ``sqrt(1 / num_freqs) / {1, sqrt(nk), nk} * scores[i].sum()`` (+ ``weights[0]`` under fit_intercept) is
+    ``features(sequence i) @ weights``.  Operands as for hipConvTokenSubstScan."""
+    (t, tab, w, r, c), host, dev, ws, wp, wn = _indel_operands(tokens, table, weights, radem, chi, seqlen, workspace)
+    g = _dev(scores, "scores", torch.float64, 2)
+    if tuple(scores.shape) != tuple(tokens.shape):
+        raise RuntimeError("Wrong array sizes.")
+    n, L = tokens.shape
+    return _lib.check(_LIB.xgpr_conv_token_window_scores_f32(
+        t, tab, w, g, r, c, C.c_void_p(host.ctypes.data), C.c_void_p(dev.data_ptr()), n, L, table.shape[0], table.shape[1],
+        chi.shape[0], radem.shape[2], int(conv_width), int(bool(fit_intercept)), wp, wn, _stream()))
+
+
+def hipConvTokenIndelScan(tokens, table, weights, scores, deletions, insertions, radem, chi, seqlen, conv_width, scaling_type,
+                          fit_intercept, workspace=None):
+    """``deletions[n, L]`` <- ``features(sequence without token p) @ weights`` minus ``features(sequence) @ weights``, and
+    ``insertions[n, L + 1, V]`` <- the same for the sequence with table row v inserted before position g (g = length appends); both
+    float64 and OVERWRITTEN, exactly +0.0 past a sequence's length, quiet NaN for the deletions of a sequence of conv_width tokens
+    (include/xgpr_hip_indel_scan.h).  ``scores`` [n, L] float64 is what hipConvTokenWindowScores wrote for the same operands.  Either
+    output may be None (that half is skipped), not both.  Shapes for which ``conv_token_indel_scan_ok`` is 0 raise RuntimeError and
+    launch nothing."""
+    (t, tab, w, r, c), host, dev, ws, wp, wn = _indel_operands(tokens, table, weights, radem, chi, seqlen, workspace)
+    n, L = tokens.shape
+    sc = _dev(scores, "scores", torch.float64, 2)
+    d = _dev(deletions, "deletions", torch.float64, 2) if deletions is not None else None
+    g = _dev(insertions, "insertions", torch.float64, 3) if insertions is not None else None
+    if tuple(scores.shape) != (n, L) or (deletions is not None and tuple(deletions.shape) != (n, L)) \
+            or (insertions is not None and tuple(insertions.shape) != (n, L + 1, table.shape[0])):
+        raise RuntimeError("Wrong array sizes.")
+    return _lib.check(_LIB.xgpr_conv_token_indel_scan_f32(
+        t, tab, w, sc, d, g, r, c, C.c_void_p(host.ctypes.data), C.c_void_p(dev.data_ptr()), n, L, table.shape[0], table.shape[1],
+        chi.shape[0], radem.shape[2], int(conv_width), int(scaling_type), int(bool(fit_intercept)), wp, wn, _stream()))
+
+
 def conv_maxpool_input_grad_ok(width):
     """Whether hipConvMaxpoolInputGrad's kernel serves a window of ``width`` = conv_width * C elements (padded width up to 1024)."""
     return int(_LIB.xgpr_conv_maxpool_input_grad_ok(int(width)))
