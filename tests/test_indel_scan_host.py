@@ -189,7 +189,8 @@ def test_every_writer_has_a_memory_contract_row():
 def test_source_id_covers_the_header(tmp_path, monkeypatch):
     bm = _build_module()
     assert os.path.samefile(bm.INDEL_SCAN_HDR, HEADER) and bm.INDEL_SCAN_HDR in bm.sources()
-    assert any(os.path.basename(p) == "indel_scan.inc" for p in bm.sources())
+    names = [os.path.basename(p) for p in bm.sources()]
+    assert "edit_scan.inc" in names and "subst_scan.inc" not in names and "indel_scan.inc" not in names
     before = bm.source_id()
     copy = tmp_path / "xgpr_hip_indel_scan.h"
     shutil.copyfile(HEADER, copy)
@@ -350,10 +351,25 @@ def test_python_wrappers():
 
 
 # ------------------------------------------------------------------------------------------------ 5. the compiler's report
+# Register-limited occupancy (waves per SIMD) of every instantiation, by mode and LOG2P = 1 .. 10: what tools/resource_usage.py reports
+# for the kernels this template replaced -- conv_token_indel_scan_kernel<lg, mode> for the modes 0 .. 2 and
+# conv_token_subst_scan_kernel<lg> for mode 3 -- at the commit before the merge.  A floor: the merged template may not fall below it.
+OCCUPANCY_FLOOR = {
+    0: [4, 3, 3, 3, 3, 3, 3, 3, 3, 3],      # window scores
+    1: [3, 3, 3, 3, 3, 3, 3, 3, 3, 2],      # deletions
+    2: [2] * 10,                            # insertions
+    3: [2] * 10,                            # substitutions
+}
+
+
 def test_the_new_kernels_use_no_scratch_and_spill_nothing():
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import resource_usage
-    rows = [r for r in resource_usage.collect() if r["name"].startswith("conv_token_indel_scan_kernel<")]
-    assert sorted(r["name"] for r in rows) == sorted(f"conv_token_indel_scan_kernel<{lg}, {mode}>" for lg in range(1, 11) for mode in range(3))
+    report = resource_usage.collect()
+    rows = [r for r in report if r["name"].startswith("conv_token_edit_scan_kernel<")]
+    assert sorted(r["name"] for r in rows) == sorted(f"conv_token_edit_scan_kernel<{lg}, {mode}>" for lg in range(1, 11) for mode in range(4))
+    assert not [r["name"] for r in report if re.match(r"conv_token_(subst|indel)_scan_kernel", r["name"])]      # the two templates it replaced
     for r in rows:
         assert r.get("ScratchSize", 0) == 0 and r.get("VGPRs Spill", 0) == 0 and r.get("SGPRs Spill", 0) == 0, r
+        lg, mode = (int(v) for v in re.fullmatch(r"conv_token_edit_scan_kernel<(\d+), (\d)>", r["name"]).groups())
+        assert r["Occupancy"] >= OCCUPANCY_FLOOR[mode][lg - 1], r

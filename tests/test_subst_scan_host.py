@@ -126,7 +126,8 @@ def test_every_writer_has_a_memory_contract_row():
 def test_source_id_covers_the_header(tmp_path, monkeypatch):
     bm = _build_module()
     assert os.path.samefile(bm.SUBST_SCAN_HDR, HEADER) and bm.SUBST_SCAN_HDR in bm.sources()
-    assert any(os.path.basename(p) == "subst_scan.inc" for p in bm.sources())
+    names = [os.path.basename(p) for p in bm.sources()]
+    assert "edit_scan.inc" in names and "subst_scan.inc" not in names and "indel_scan.inc" not in names
     before = bm.source_id()
     copy = tmp_path / "xgpr_hip_subst_scan.h"
     shutil.copyfile(HEADER, copy)
@@ -257,7 +258,7 @@ def test_python_wrappers():
 def test_the_new_kernels_use_no_scratch_and_spill_nothing():
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import resource_usage
-    rows = [r for r in resource_usage.collect() if r["name"].startswith("conv_token_subst_scan_kernel<")]
-    assert sorted(r["name"] for r in rows) == sorted(f"conv_token_subst_scan_kernel<{lg}>" for lg in range(1, 11))
+    rows = [r for r in resource_usage.collect() if re.fullmatch(r"conv_token_edit_scan_kernel<\d+, 3>", r["name"])]      # mode 3 = EDIT_SUBST
+    assert sorted(r["name"] for r in rows) == sorted(f"conv_token_edit_scan_kernel<{lg}, 3>" for lg in range(1, 11))
     for r in rows:
         assert r.get("ScratchSize", 0) == 0 and r.get("VGPRs Spill", 0) == 0 and r.get("SGPRs Spill", 0) == 0, r

@@ -222,7 +222,7 @@ template <int LOG2P> struct TokenWindows {
     }
 };
 
-// SubstTokenWindows: TokenWindows with one more way to complete a fetch (the substitution scan, subst_scan.inc).  take_subst(v, q, tok)
+// SubstTokenWindows: TokenWindows with one more way to complete a fetch (the substitution scan, edit_scan.inc).  take_subst(v, q, tok)
 // is take(v) on the window whose token at position offset q is `tok`: the registers whose position offset equals q gather from table
 // row `tok`, every other register from the row of the byte it fetched.  Padded registers carry the offset 0xffff and never match.  The
 // fetched bytes are left as they are: one issue(j) serves every variant of window j.
@@ -240,7 +240,7 @@ template <int LOG2P> struct SubstTokenWindows : TokenWindows<LOG2P> {
     }
 };
 
-// IndelTokenWindows: the windows of a sequence with ONE token deleted or inserted (the indel scan, indel_scan.inc), fetched from the
+// IndelTokenWindows: the windows of a sequence with ONE token deleted or inserted (the indel scan, edit_scan.inc), fetched from the
 // original bytes by remapping each register's position offset -- no mutant is written.  Window jm of the mutant starts at the original
 // byte jm, and q is the edit's position offset inside it.
 //   issue_del(jm, q)   offset k reads the original k + (k >= q): the tokens before the deleted one, then those after it.  The range

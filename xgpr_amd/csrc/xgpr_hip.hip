@@ -72,8 +72,7 @@ namespace {
 #include "launchers.inc"
 #include "input_grad.inc"
 #include "seq_input_grad.inc"
-#include "subst_scan.inc"
-#include "indel_scan.inc"
+#include "edit_scan.inc"
 #include "pool_input_grad.inc"
 #include "cluster.inc"
 

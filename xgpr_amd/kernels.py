@@ -573,6 +573,10 @@ class ConvSORFKernel(KernelBase):
             raise RuntimeError("weights must be one vector of num_rffs values.")
         return xs, lengths, w
 
+    def _scan_operator_ok(self, xs, predicate):
+        return bool(xs.is_cuda and xs.tokens.is_contiguous()
+                    and predicate(self.conv_width * xs.shape[2], xs.table.shape[0], xs.shape[2], self.num_freqs) == 1)
+
     def substitution_scan(self, batch, sequence_length, weights):
         """float64 device tensor [n, L, V]: ``transform_x(sequence with token l replaced by v) @ weights`` minus
         ``transform_x(sequence) @ weights`` for every position l and every row v of the TokenBatch's table -- the exact effect of
@@ -583,10 +587,9 @@ class ConvSORFKernel(KernelBase):
         of more than 1024 elements, a table the LDS image does not hold) or the tokens are not contiguous the result comes from
         ``substitution_scan_composed``."""
         xs, lengths, w = self._scan_inputs(batch, sequence_length, weights)
-        n, L, C = xs.shape
+        n, L, _ = xs.shape
         V = xs.table.shape[0]
-        if not (xs.is_cuda and xs.tokens.is_contiguous()
-                and ext.conv_token_subst_scan_ok(self.conv_width * C, V, C, self.num_freqs) == 1):
+        if not self._scan_operator_ok(xs, ext.conv_token_subst_scan_ok):
             return self._scan_composed(xs, lengths, w)
         out = torch.empty((n, L, V), dtype=torch.float64, device=self.device)
         ext.hipConvTokenSubstScan(xs.tokens, xs.table.contiguous(), w, out, self.radem_diag, self.chi_arr, lengths, self.conv_width,
@@ -602,27 +605,15 @@ class ConvSORFKernel(KernelBase):
 
     def _scan_composed(self, xs, lengths, w):
         n, L, _ = xs.shape
-        V, M, dev = xs.table.shape[0], self.num_rffs, self.device
-        if n and (int(lengths.min()) < self.conv_width or int(lengths.max()) > L):
-            raise RuntimeError("All sequence lengths must be >= conv width and < array size.")
+        V, dev = xs.table.shape[0], self.device
+        self._check_lengths(lengths, n, L)
+        project = self._projector(xs.table, w)
         tokens, lens_dev = xs.tokens.contiguous(), torch.from_numpy(lengths).to(dev)
-        wcol = w.clone()
-        if self.fit_intercept:
-            wcol[0] = 0.                                 # column 0 is the constant 1 of both rows
-        wcol = wcol[:, None].contiguous()
-        step = max(1, self.COMPOSED_SCAN_ELEMS // M)
-
-        def project(tok, seq_ids):
-            rows = torch.empty((tok.shape[0], M), dtype=torch.float32, device=dev)
-            self.fill_feature_rows(TokenBatch(tok, xs.table), lengths[seq_ids.cpu().numpy()], rows)
-            val = torch.empty((tok.shape[0], 1), dtype=torch.float64, device=dev)
-            ext.hipZCacheBlockProject(rows, wcol, val, False, 1.0)
-            return val[:, 0]
+        step = max(1, self.COMPOSED_SCAN_ELEMS // self.num_rffs)
 
         base = torch.empty(n, dtype=torch.float64, device=dev)
         for lo in range(0, n, step):
-            ids = torch.arange(lo, min(lo + step, n), device=dev)
-            base[lo:lo + step] = project(tokens[ids], ids)
+            base[lo:lo + step] = project(tokens[lo:lo + step], lengths[lo:lo + step])
         out = torch.empty((n, L, V), dtype=torch.float64, device=dev)
         flat = out.view(-1)
         for lo in range(0, n * L * V, step):
@@ -630,17 +621,13 @@ class ConvSORFKernel(KernelBase):
             seq, pos, tok = ids // (L * V), (ids // V) % L, ids % V
             mut = tokens[seq]
             mut[torch.arange(ids.shape[0], device=dev), pos] = tok.to(torch.uint8)
-            flat[lo:lo + step] = project(mut, seq) - base[seq]
+            flat[lo:lo + step] = project(mut, lengths[seq.cpu().numpy()]) - base[seq]
         # the own token and the positions past a length: the mutant is the sequence itself
         pos = torch.arange(L, device=dev)
         same = (pos[None, :] >= lens_dev[:, None])[:, :, None] | (torch.arange(V, device=dev)[None, None, :] == tokens.long()[:, :, None])
         return out.masked_fill_(same, 0.0)
 
     # ---- the exact effect of every single-token deletion and insertion on a weighted sum of the features
-    def _indel_operator_ok(self, xs):
-        return bool(xs.is_cuda and xs.tokens.is_contiguous()
-                    and ext.conv_token_indel_scan_ok(self.conv_width * xs.shape[2], xs.table.shape[0], xs.shape[2], self.num_freqs) == 1)
-
     def window_scores(self, batch, sequence_length, weights):
         """float64 device tensor [n, L]: the share of every k-mer window in ``transform_x(sequence) @ weights`` before the k-mer
         normaliser -- ``scores[i, j] = sum_f (w[2f] cos p_f + w[2f+1] sin p_f)`` over the projections p of window j
@@ -649,7 +636,7 @@ class ConvSORFKernel(KernelBase):
         ``transform_x(sequence i) @ weights``.  One HIP kernel (``ext.hipConvTokenWindowScores``) where
         ``ext.conv_token_indel_scan_ok`` holds; elsewhere every window goes through ``fill_feature_rows`` as a sequence of its own."""
         xs, lengths, w = self._scan_inputs(batch, sequence_length, weights)
-        if not self._indel_operator_ok(xs):
+        if not self._scan_operator_ok(xs, ext.conv_token_indel_scan_ok):
             return self._window_scores_composed(xs, lengths, w)
         scores = torch.empty(xs.shape[:2], dtype=torch.float64, device=self.device)
         ext.hipConvTokenWindowScores(xs.tokens, xs.table.contiguous(), w, scores, self.radem_diag, self.chi_arr, lengths, self.conv_width,
@@ -666,7 +653,7 @@ class ConvSORFKernel(KernelBase):
         k-mer normaliser, and write no mutant; where ``ext.conv_token_indel_scan_ok`` is 0 or the tokens are not contiguous the
         result comes from ``indel_scan_composed``."""
         xs, lengths, w = self._scan_inputs(batch, sequence_length, weights)
-        if not self._indel_operator_ok(xs):
+        if not self._scan_operator_ok(xs, ext.conv_token_indel_scan_ok):
             return self._indel_composed(xs, lengths, w)
         n, L, _ = xs.shape
         table = xs.table.contiguous()

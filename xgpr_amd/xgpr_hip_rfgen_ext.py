@@ -1047,47 +1047,7 @@ def hipConvTokenInputGrad(tokens, table, weights, out, radem, chi, seqlen, sigma
         int(scaling_type), int(bool(fit_intercept)), wp, wn, _stream()))
 
 
-def conv_token_subst_scan_ok(width, vocab, C, num_freqs):
-    """Whether hipConvTokenSubstScan's kernel serves a window of ``width`` = conv_width * C elements over a table of ``vocab``
-    rows and ``C`` columns (padded width up to 1024, a table the LDS image holds); no device work."""
-    return int(_LIB.xgpr_conv_token_subst_scan_ok(int(width), int(vocab), int(C), int(num_freqs)))
-
-
-def hipConvTokenSubstScan(tokens, table, weights, out, radem, chi, seqlen, conv_width, scaling_type, fit_intercept, workspace=None):
-    """``out[n, L, V]`` (float64, OVERWRITTEN) <- ``features(sequence with token l replaced by v) @ weights`` minus
-    ``features(sequence) @ weights`` for every position l and token v of the sequence and graph kernels
-    (include/xgpr_hip_subst_scan.h): exactly +0.0 at a sequence's own token and past its length.  ``tokens`` [n, L] uint8 index
-    the rows of ``table`` [V, C] float32 (already sigma-scaled); ``weights`` float64 [2 * num_freqs], one vector for all
-    sequences (``weights[0]`` is ignored under fit_intercept); ``seqlen`` int32 on the host.  Shapes for which
-    ``conv_token_subst_scan_ok`` is 0 raise RuntimeError and launch nothing."""
-    t = _dev(tokens, "tokens", torch.uint8, 2)
-    tab = _dev(table, "table", torch.float32, 2)
-    w = _dev(weights, "weights", torch.float64, 1)
-    g = _dev(out, "out", torch.float64, 3)
-    r = _radem3(radem)
-    c = _dev(chi, "chi", torch.float32, 1)
-    n, L = tokens.shape
-    if tuple(out.shape) != (n, L, table.shape[0]) or weights.shape[0] != 2 * chi.shape[0]:
-        raise RuntimeError("Wrong array sizes.")
-    host, dev = _seqlens(seqlen, tokens.device)
-    if host.shape[0] != n:
-        raise RuntimeError("wrong array sizes")
-    if workspace is None:
-        ws, wp, wn = _workspace(_LIB.xgpr_rbf_workspace_bytes(radem.shape[2]), tokens.device)
-    else:
-        ws, wp, wn = workspace, C.c_void_p(workspace.data_ptr()), C.c_size_t(workspace.numel() * workspace.element_size())
-    return _lib.check(_LIB.xgpr_conv_token_subst_scan_f32(
-        t, tab, w, g, r, c, C.c_void_p(host.ctypes.data), C.c_void_p(dev.data_ptr()), n, L, table.shape[0], table.shape[1],
-        chi.shape[0], radem.shape[2], int(conv_width), int(scaling_type), int(bool(fit_intercept)), wp, wn, _stream()))
-
-
-def conv_token_indel_scan_ok(width, vocab, C, num_freqs):
-    """Whether the kernels of hipConvTokenWindowScores / hipConvTokenIndelScan serve a window of ``width`` = conv_width * C elements over
-    a table of ``vocab`` rows and ``C`` columns (where ``conv_token_subst_scan_ok`` is 1); no device work."""
-    return int(_LIB.xgpr_conv_token_indel_scan_ok(int(width), int(vocab), int(C), int(num_freqs)))
-
-
-def _indel_operands(tokens, table, weights, radem, chi, seqlen, workspace):
+def _scan_operands(tokens, table, weights, radem, chi, seqlen, workspace):
     ops = (_dev(tokens, "tokens", torch.uint8, 2), _dev(table, "table", torch.float32, 2), _dev(weights, "weights", torch.float64, 1),
            _radem3(radem), _dev(chi, "chi", torch.float32, 1))
     if weights.shape[0] != 2 * chi.shape[0]:
@@ -1102,12 +1062,41 @@ def _indel_operands(tokens, table, weights, radem, chi, seqlen, workspace):
     return ops, host, dev, ws, wp, wn
 
 
+def conv_token_subst_scan_ok(width, vocab, C, num_freqs):
+    """Whether hipConvTokenSubstScan's kernel serves a window of ``width`` = conv_width * C elements over a table of ``vocab``
+    rows and ``C`` columns (padded width up to 1024, a table the LDS image holds); no device work."""
+    return int(_LIB.xgpr_conv_token_subst_scan_ok(int(width), int(vocab), int(C), int(num_freqs)))
+
+
+def hipConvTokenSubstScan(tokens, table, weights, out, radem, chi, seqlen, conv_width, scaling_type, fit_intercept, workspace=None):
+    """``out[n, L, V]`` (float64, OVERWRITTEN) <- ``features(sequence with token l replaced by v) @ weights`` minus
+    ``features(sequence) @ weights`` for every position l and token v of the sequence and graph kernels
+    (include/xgpr_hip_subst_scan.h): exactly +0.0 at a sequence's own token and past its length.  ``tokens`` [n, L] uint8 index
+    the rows of ``table`` [V, C] float32 (already sigma-scaled); ``weights`` float64 [2 * num_freqs], one vector for all
+    sequences (``weights[0]`` is ignored under fit_intercept); ``seqlen`` int32 on the host.  Shapes for which
+    ``conv_token_subst_scan_ok`` is 0 raise RuntimeError and launch nothing."""
+    (t, tab, w, r, c), host, dev, ws, wp, wn = _scan_operands(tokens, table, weights, radem, chi, seqlen, workspace)
+    g = _dev(out, "out", torch.float64, 3)
+    n, L = tokens.shape
+    if tuple(out.shape) != (n, L, table.shape[0]):
+        raise RuntimeError("Wrong array sizes.")
+    return _lib.check(_LIB.xgpr_conv_token_subst_scan_f32(
+        t, tab, w, g, r, c, C.c_void_p(host.ctypes.data), C.c_void_p(dev.data_ptr()), n, L, table.shape[0], table.shape[1],
+        chi.shape[0], radem.shape[2], int(conv_width), int(scaling_type), int(bool(fit_intercept)), wp, wn, _stream()))
+
+
+def conv_token_indel_scan_ok(width, vocab, C, num_freqs):
+    """Whether the kernels of hipConvTokenWindowScores / hipConvTokenIndelScan serve a window of ``width`` = conv_width * C elements over
+    a table of ``vocab`` rows and ``C`` columns (where ``conv_token_subst_scan_ok`` is 1); no device work."""
+    return int(_LIB.xgpr_conv_token_indel_scan_ok(int(width), int(vocab), int(C), int(num_freqs)))
+
+
 def hipConvTokenWindowScores(tokens, table, weights, scores, radem, chi, seqlen, conv_width, fit_intercept, workspace=None):
     """``scores[n, L]`` (float64, OVERWRITTEN) <- the score of every k-mer window of the sequence and graph kernels
     (include/xgpr_hip_indel_scan.h): ``scores[i, j] = sum_f (w[2f] cos p_f + w[2f+1] sin p_f)`` over the projections p of window j,
     exactly +0.0 for j >= nk.  ``sqrt(1 / num_freqs) / {1, sqrt(nk), nk} * scores[i].sum()`` (+ ``weights[0]`` under fit_intercept) is
     ``features(sequence i) @ weights``.  Operands as for hipConvTokenSubstScan."""
-    (t, tab, w, r, c), host, dev, ws, wp, wn = _indel_operands(tokens, table, weights, radem, chi, seqlen, workspace)
+    (t, tab, w, r, c), host, dev, ws, wp, wn = _scan_operands(tokens, table, weights, radem, chi, seqlen, workspace)
     g = _dev(scores, "scores", torch.float64, 2)
     if tuple(scores.shape) != tuple(tokens.shape):
         raise RuntimeError("Wrong array sizes.")
@@ -1125,7 +1114,7 @@ def hipConvTokenIndelScan(tokens, table, weights, scores, deletions, insertions,
     (include/xgpr_hip_indel_scan.h).  ``scores`` [n, L] float64 is what hipConvTokenWindowScores wrote for the same operands.  Either
     output may be None (that half is skipped), not both.  Shapes for which ``conv_token_indel_scan_ok`` is 0 raise RuntimeError and
     launch nothing."""
-    (t, tab, w, r, c), host, dev, ws, wp, wn = _indel_operands(tokens, table, weights, radem, chi, seqlen, workspace)
+    (t, tab, w, r, c), host, dev, ws, wp, wn = _scan_operands(tokens, table, weights, radem, chi, seqlen, workspace)
     n, L = tokens.shape
     sc = _dev(scores, "scores", torch.float64, 2)
     d = _dev(deletions, "deletions", torch.float64, 2) if deletions is not None else None
