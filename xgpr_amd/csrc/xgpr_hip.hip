@@ -52,6 +52,7 @@ typedef enum { ncclFloat64 = 8 } ncclDataType_t;
 #include "../../include/xgpr_hip_cluster.h"
 #include "../../include/xgpr_hip_subst_scan.h"
 #include "../../include/xgpr_hip_indel_scan.h"
+#include "../../include/xgpr_hip_subst_var_scan.h"
 
 namespace {
 
@@ -73,6 +74,7 @@ namespace {
 #include "input_grad.inc"
 #include "seq_input_grad.inc"
 #include "edit_scan.inc"
+#include "subst_var_scan.inc"
 #include "pool_input_grad.inc"
 #include "cluster.inc"
 
@@ -614,6 +616,22 @@ int xgpr_conv_token_indel_scan_f32(const uint8_t *tokens, const float *table, co
                                    void *stream) {
     return indel_scan_impl(tokens, table, w, scores, del, ins, radem, chi, seqlen_host, seqlen_dev, n, L, vocab, C, num_freqs,
                            radem_shape2, conv_width, scaling_type, fit_intercept, workspace, workspace_bytes, stream);
+}
+
+// ---- include/xgpr_hip_subst_var_scan.h
+int xgpr_conv_token_subst_var_scan_ok(long width, long vocab, long C, long num_freqs, long nvar) {
+    return conv_token_subst_var_scan_ok_impl(width, vocab, C, num_freqs, nvar);
+}
+size_t xgpr_conv_token_subst_var_scan_workspace_bytes(long radem_shape2, long nvar, long slab_rows) {
+    return conv_token_subst_var_scan_workspace_bytes_impl(radem_shape2, nvar, slab_rows);
+}
+int xgpr_conv_token_subst_var_scan_f32(const uint8_t *tokens, const float *table, const double *vm, long vm_stride, const double *u,
+                                       const double *q, double *out, const int8_t *radem, const float *chi, const int32_t *seqlen_host,
+                                       const int32_t *seqlen_dev, long n, long L, long vocab, long C, long num_freqs, long radem_shape2,
+                                       long nvar, int conv_width, int scaling_type, int fit_intercept, long slab_rows, void *workspace,
+                                       size_t workspace_bytes, void *stream) {
+    return subst_var_scan_impl(tokens, table, vm, vm_stride, u, q, out, radem, chi, seqlen_host, seqlen_dev, n, L, vocab, C, num_freqs,
+                               radem_shape2, nvar, conv_width, scaling_type, fit_intercept, slab_rows, workspace, workspace_bytes, stream);
 }
 
 int xgpr_selftest_lane_xor(int32_t *out, void *stream) {

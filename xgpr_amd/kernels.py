@@ -627,6 +627,83 @@ class ConvSORFKernel(KernelBase):
         same = (pos[None, :] >= lens_dev[:, None])[:, :, None] | (torch.arange(V, device=dev)[None, None, :] == tokens.long()[:, :, None])
         return out.masked_fill_(same, 0.0)
 
+    # ---- the exact quadratic form of the predictive variance of every single-token substitution
+    def _var_scan_inputs(self, batch, sequence_length, var):
+        if not isinstance(batch, TokenBatch):
+            raise RuntimeError("substitution_variance_scan needs sequences given as tokens (a TokenBatch).")
+        xs = self.scaled_f32(batch)
+        lengths = self._host_lengths(xs, sequence_length)
+        if lengths.shape[0] != xs.shape[0]:
+            raise RuntimeError("sequence_length must hold one length per sequence.")
+        vm = var if isinstance(var, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(var))
+        vm = vm.to(self.device, torch.float64)
+        if vm.dim() != 2 or vm.shape[0] != vm.shape[1] or not 1 <= vm.shape[0] <= self.num_rffs:
+            raise RuntimeError("var must be a square matrix over the first 1 .. num_rffs feature columns.")
+        return xs, lengths, vm
+
+    def substitution_variance_scan(self, batch, sequence_length, var):
+        """float64 device tensor [n, L, V]: ``z'^T var z'`` for the first ``nvar = var.shape[0]`` columns z' of
+        ``transform_x(sequence with token l replaced by v)``, for every position l and every row v of the TokenBatch's table --
+        what ``xGPRegression.predict`` turns into the variance (lambda^2 + lambda^2 z'^T var z').  Exactly 0 past a sequence's
+        length; the sequence's own quadratic form at its own token.  A substitution at l moves z by r times a vector built from
+        the conv_width windows that cover l alone, so one pair of HIP kernels per slab of mutants (``ext.hipConvTokenSubstVarScan``)
+        transforms L V conv_width windows of one 1024-frequency tile and contracts the [L V, nvar] matrix of those vectors with
+        ``var`` on the float64 matrix cores; the sequences' own columns come from ``fill_feature_rows`` (float32 rows, widened).
+        An odd nvar is padded with a zero row and column.  Where ``ext.conv_token_subst_var_scan_ok`` is 0 (windows of more than
+        1024 elements, a table the LDS image does not hold, nvar > 2048) or the tokens are not contiguous the result comes from
+        ``substitution_variance_scan_composed``."""
+        xs, lengths, vm = self._var_scan_inputs(batch, sequence_length, var)
+        n, L, C = xs.shape
+        V, nvar = xs.table.shape[0], vm.shape[0]
+        npad = nvar + (nvar & 1)
+        if not (xs.is_cuda and xs.tokens.is_contiguous()
+                and ext.conv_token_subst_var_scan_ok(self.conv_width * C, V, C, self.num_freqs, npad) == 1):
+            return self._var_scan_composed(xs, lengths, vm)
+        vp = torch.zeros((npad, npad), dtype=torch.float64, device=self.device)
+        vp[:nvar, :nvar] = vm
+        rows = torch.empty((n, self.num_rffs), dtype=torch.float32, device=self.device)
+        self.fill_feature_rows(xs, lengths, rows)
+        z = rows[:, :npad].to(torch.float64)
+        zv = z @ vp.T                                    # row i: var z_i
+        u = (0.5 * (zv + z @ vp)).contiguous()           # (= var z_i for a symmetric var; the cross terms of any var)
+        q = (z * zv).sum(dim=1).contiguous()
+        out = torch.empty((n, L, V), dtype=torch.float64, device=self.device)
+        ext.hipConvTokenSubstVarScan(xs.tokens, xs.table.contiguous(), vp, u, q, out, self.radem_diag, self.chi_arr, lengths,
+                                     self.conv_width, self.scaling_type, self.fit_intercept)
+        return out
+
+    def substitution_variance_scan_composed(self, batch, sequence_length, var):
+        """The same result from existing operators, at every window width, table size and nvar: a bounded slice of (sequence,
+        position, token) mutants is written out as token rows, ``fill_feature_rows`` makes their float32 feature rows, and the
+        quadratic form of their first nvar columns with ``var`` is taken in float64 with torch.  At most ``COMPOSED_SCAN_ELEMS``
+        float32 row elements are held at a time."""
+        return self._var_scan_composed(*self._var_scan_inputs(batch, sequence_length, var))
+
+    def _var_scan_composed(self, xs, lengths, vm):
+        n, L, _ = xs.shape
+        V, dev, nvar = xs.table.shape[0], self.device, vm.shape[0]
+        self._check_lengths(lengths, n, L)
+        tokens, lens_dev = xs.tokens.contiguous(), torch.from_numpy(lengths).to(dev)
+        step = max(1, self.COMPOSED_SCAN_ELEMS // self.num_rffs)
+
+        def quad(tok, lens):
+            rows = torch.empty((tok.shape[0], self.num_rffs), dtype=torch.float32, device=dev)
+            self.fill_feature_rows(TokenBatch(tok.contiguous(), xs.table), lens, rows)
+            xv = rows[:, :nvar].to(torch.float64)
+            return (xv * (xv @ vm.T)).sum(dim=1)
+
+        out = torch.empty((n, L, V), dtype=torch.float64, device=dev)
+        flat = out.view(-1)
+        for lo in range(0, n * L * V, step):
+            ids = torch.arange(lo, min(lo + step, n * L * V), device=dev)
+            seq, pos, tok = ids // (L * V), (ids // V) % L, ids % V
+            mut = tokens[seq]
+            # (a position past the length: the token lands outside the sequence and is never read; zeroed below)
+            mut[torch.arange(ids.shape[0], device=dev), pos] = tok.to(torch.uint8)
+            flat[lo:lo + step] = quad(mut, lengths[seq.cpu().numpy()])
+        past = torch.arange(L, device=dev)[None, :] >= lens_dev[:, None]
+        return out.masked_fill_(past[:, :, None], 0.0)
+
     # ---- the exact effect of every single-token deletion and insertion on a weighted sum of the features (DESIGN.md 3.21)
     def window_scores(self, batch, sequence_length, weights):
         """float64 device tensor [n, L]: the share of every k-mer window in ``transform_x(sequence) @ weights`` before the k-mer

@@ -222,7 +222,7 @@ class xGPRegression(_ModelBase):
             return gmean
         return gmean, torch.cat(gvar).cpu().numpy() * self.trainy_std ** 2
 
-    def predict_substitutions(self, input_x, sequence_lengths=None, token_table=None, chunk_size=64):
+    def predict_substitutions(self, input_x, sequence_lengths=None, token_table=None, chunk_size=64, get_var=False):
         """The exact effect of every single substitution on ``predict`` (no counterpart in the reference) -> numpy float64
         [N, L, V]: entry [i, l, v] is the predicted mean of sequence i with its token at position l replaced by row v of the
         token table, minus the predicted mean of sequence i itself, in the units of y (times the training y's standard
@@ -232,10 +232,16 @@ class xGPRegression(_ModelBase):
         sum over k-mer windows: a substitution changes only the conv_width windows that cover it, so the scan costs
         L V conv_width window transforms, not the L V (L - conv_width + 1) of L V mutant sequences, and no mutant is written
         (``predict_gradient`` gives the first-order estimate).  ``chunk_size`` sequences go to the device at a
-        time.  The VARIANCE of the mutants is not covered: it is a quadratic form of the whole feature row and has no
-        per-window decomposition."""
+        time.  With ``get_var=True`` the return is (scan, variances): variances[i, l, v] is the predictive VARIANCE of that
+        mutant as ``predict(get_var=True)`` gives it -- trainy_std^2 max(0, lambda^2 + lambda^2 z'^T var z') --, exactly 0 past a
+        sequence's length and the sequence's own variance at its own token.  It has a per-window decomposition too: the
+        substitution moves the variance columns z by a vector built from the conv_width covering windows alone, so the quadratic
+        form needs those windows' first tile and one nvar x nvar contraction per mutant, not the mutants' feature rows
+        (``ConvSORFKernel.substitution_variance_scan``)."""
         if self.weights is None:
             raise RuntimeError("Model has not yet been successfully fitted.")
+        if get_var and self.var is None:
+            raise RuntimeError("Variance was requested but suppress_var was selected when fitting.")
         if type(self.kernel) is not ConvSORFKernel:
             raise RuntimeError("predict_substitutions is available for the sequence and graph kernels Conv1dRBF, Conv1dMatern, "
                                "Conv1dCauchy, GraphRBF, GraphMatern and GraphCauchy on token input; Conv1dTwoLayer, the "
@@ -251,9 +257,19 @@ class xGPRegression(_ModelBase):
             raise RuntimeError("The shape[0] of sequence_lengths must match the shape[0] of input_x.")
         scans = [self.kernel.substitution_scan(input_x[i:i + chunk_size], sequence_lengths[i:i + chunk_size], self.weights)
                  for i in range(0, input_x.shape[0], chunk_size)]
-        if not scans:
-            return np.zeros((0, input_x.shape[1], input_x.table.shape[0]))
-        return torch.cat(scans).cpu().numpy() * self.trainy_std
+        scan = (torch.cat(scans).cpu().numpy() * self.trainy_std if scans
+                else np.zeros((0, input_x.shape[1], input_x.table.shape[0])))
+        if not get_var:
+            return scan
+        lambda_ = float(self.kernel.get_lambda())
+        quads = [self.kernel.substitution_variance_scan(input_x[i:i + chunk_size], sequence_lengths[i:i + chunk_size], self.var)
+                 for i in range(0, input_x.shape[0], chunk_size)]
+        if not quads:
+            return scan, np.zeros(scan.shape)
+        var = lambda_ ** 2 + lambda_ ** 2 * torch.cat(quads).cpu().numpy()
+        var[var < 0] = 0
+        var[np.arange(input_x.shape[1])[None, :] >= sequence_lengths[:, None]] = 0
+        return scan, var * self.trainy_std ** 2
 
     def _token_scan_input(self, name, input_x, sequence_lengths, token_table):
         """The refusals ``predict_substitutions`` makes, for the other position-by-position scans -> (TokenBatch, lengths)."""
@@ -283,7 +299,8 @@ class xGPRegression(_ModelBase):
         a sequence of exactly conv_width tokens, whose mutant has no k-mer.  Input and kernels as for ``predict_substitutions``.
         An indel only shifts the windows away from the edit, so the scan transforms about conv_width windows per edit plus
         the sequence's own windows once, and rescales the total by the mutant's k-mer normaliser; no mutant is written
-        (DESIGN.md 3.21).  The VARIANCE of the mutants is not covered."""
+        (DESIGN.md 3.21).  The VARIANCE of the indel mutants is not built yet: the identity of ``predict_substitutions(get_var=True)``
+        holds there too, with the mutant's normaliser r' and the shifted window set."""
         input_x, sequence_lengths = self._token_scan_input("predict_indels", input_x, sequence_lengths, token_table)
         scans = [self.kernel.indel_scan(input_x[i:i + chunk_size], sequence_lengths[i:i + chunk_size], self.weights)
                  for i in range(0, input_x.shape[0], chunk_size)]

@@ -1085,6 +1085,56 @@ def hipConvTokenSubstScan(tokens, table, weights, out, radem, chi, seqlen, conv_
         chi.shape[0], radem.shape[2], int(conv_width), int(scaling_type), int(bool(fit_intercept)), wp, wn, _stream()))
 
 
+def conv_token_subst_var_scan_ok(width, vocab, C, num_freqs, nvar):
+    """Whether hipConvTokenSubstVarScan's kernels serve the shape: where ``conv_token_subst_scan_ok`` is 1 and ``nvar`` is even,
+    at least 2 and at most min(2 * num_freqs, 2048); no device work."""
+    return int(_LIB.xgpr_conv_token_subst_var_scan_ok(int(width), int(vocab), int(C), int(num_freqs), int(nvar)))
+
+
+def conv_token_subst_var_scan_workspace_bytes(radem_shape2, nvar, slab_rows=0):
+    """The exact workspace of hipConvTokenSubstVarScan in bytes: the packed sign masks and ``slab_rows`` float64 rows of ``nvar``
+    columns (0: the library's default)."""
+    return int(_LIB.xgpr_conv_token_subst_var_scan_workspace_bytes(int(radem_shape2), int(nvar), int(slab_rows)))
+
+
+def hipConvTokenSubstVarScan(tokens, table, vm, u, q, out, radem, chi, seqlen, conv_width, scaling_type, fit_intercept, slab_rows=0,
+                             workspace=None):
+    """``out[n, L, V]`` (float64, OVERWRITTEN) <- ``z'^T vm z'`` over the first ``nvar = vm.shape[0]`` feature columns z' of the
+    sequence with token l replaced by v, for every position l and token v of the sequence and graph kernels
+    (include/xgpr_hip_subst_var_scan.h): ``q[i]`` bit for bit at a sequence's own token, exactly 0.0 past its length.  ``vm``
+    float64 [nvar, nvar] (rows may be strided; nvar even), ``u`` [n, nvar] = the sequences' columns times vm and ``q`` [n] = their
+    quadratic forms, both float64 and precomputed by the caller.  ``slab_rows`` mutant rows are held in the workspace at a time
+    (0: the default -- the library's, or the call's own n L V rows where those are fewer --; otherwise a multiple of 16; the result
+    does not depend on it).  Shapes for which ``conv_token_subst_var_scan_ok`` is 0 raise RuntimeError and launch nothing."""
+    t, tab = _dev(tokens, "tokens", torch.uint8, 2), _dev(table, "table", torch.float32, 2)
+    r, c = _radem3(radem), _dev(chi, "chi", torch.float32, 1)
+    g = _dev(out, "out", torch.float64, 3)
+    n, L = tokens.shape
+    if vm.dim() != 2 or vm.dtype != torch.float64 or not vm.is_cuda or vm.shape[0] != vm.shape[1] or vm.stride(1) != 1:
+        raise RuntimeError("vm must be a float64 device matrix [nvar, nvar] with contiguous rows.")
+    nvar = vm.shape[0]
+    uu, qq = _dev(u, "u", torch.float64, 2), _dev(q, "q", torch.float64, 1)
+    if tuple(out.shape) != (n, L, table.shape[0]) or tuple(u.shape) != (n, nvar) or q.shape[0] != n:
+        raise RuntimeError("Wrong array sizes.")
+    host, dev = _seqlens(seqlen, tokens.device)
+    if host.shape[0] != n:
+        raise RuntimeError("wrong array sizes")
+    if workspace is None:
+        if slab_rows == 0 and nvar >= 2 and nvar % 2 == 0:
+            # (a call with fewer mutant rows than the default slab holds allocates no more than its rows: the slab size does not enter the result)
+            masks = int(_LIB.xgpr_rbf_workspace_bytes(radem.shape[2]))
+            default = (conv_token_subst_var_scan_workspace_bytes(radem.shape[2], nvar, 0) - masks) // (8 * nvar)
+            rows = max(16, -(-n * L * table.shape[0] // 16) * 16)
+            slab_rows = rows if rows < default else 0
+        ws, wp, wn = _workspace(conv_token_subst_var_scan_workspace_bytes(radem.shape[2], nvar, slab_rows), tokens.device)
+    else:
+        ws, wp, wn = workspace, C.c_void_p(workspace.data_ptr()), C.c_size_t(workspace.numel() * workspace.element_size())
+    return _lib.check(_LIB.xgpr_conv_token_subst_var_scan_f32(
+        t, tab, C.c_void_p(vm.data_ptr()), vm.stride(0), uu, qq, g, r, c, C.c_void_p(host.ctypes.data),
+        C.c_void_p(dev.data_ptr()), n, L, table.shape[0], table.shape[1], chi.shape[0], radem.shape[2], nvar, int(conv_width),
+        int(scaling_type), int(bool(fit_intercept)), int(slab_rows), wp, wn, _stream()))
+
+
 def conv_token_indel_scan_ok(width, vocab, C, num_freqs):
     """Whether the kernels of hipConvTokenWindowScores / hipConvTokenIndelScan serve a window of ``width`` = conv_width * C elements over
     a table of ``vocab`` rows and ``C`` columns (where ``conv_token_subst_scan_ok`` is 1); no device work."""
