@@ -143,6 +143,13 @@ SUBST_VAR_SCAN_SIGNATURES = {
     "xgpr_conv_token_subst_var_scan_f32": [_vp, _vp, _vp, _l, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _l, _l, _l, _l, _l, _l, _l, _i, _i, _i, _l,
                                            _vp, _sz, _vp],
 }
+# ... and include/xgpr_hip_indel_var_scan.h, the tenth (tests/test_indel_var_scan_host.py); its *_workspace_bytes function returns size_t
+INDEL_VAR_SCAN_SIGNATURES = {
+    "xgpr_conv_token_indel_var_scan_ok": [_l, _l, _l, _l, _l],
+    "xgpr_conv_token_indel_var_scan_workspace_bytes": [_l, _l, _l],
+    "xgpr_conv_token_indel_var_scan_f32": [_vp, _vp, _vp, _l, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _l, _l, _l, _l, _l, _l, _l,
+                                           _i, _i, _i, _l, _vp, _sz, _vp],
+}
 STRING_FUNCS = ["xgpr_last_error", "xgpr_build_arch", "xgpr_build_id"]
 
 _lib = None
@@ -164,10 +171,11 @@ def load():
     for name, args in (list(SIGNATURES.items()) + list(POOL_SIGNATURES.items()) + list(INPUT_GRAD_SIGNATURES.items())
                        + list(SEQ_INPUT_GRAD_SIGNATURES.items()) + list(POOL_INPUT_GRAD_SIGNATURES.items()) + list(CLUSTER_SIGNATURES.items())
                        + list(SUBST_SCAN_SIGNATURES.items()) + list(INDEL_SCAN_SIGNATURES.items())
-                       + list(SUBST_VAR_SCAN_SIGNATURES.items())):
+                       + list(SUBST_VAR_SCAN_SIGNATURES.items()) + list(INDEL_VAR_SCAN_SIGNATURES.items())):
         fn = getattr(lib, name)
         fn.argtypes = args
-        fn.restype = C.c_size_t if (name in CLUSTER_SIGNATURES or name in SUBST_VAR_SCAN_SIGNATURES) and name.endswith("_workspace_bytes") else C.c_int
+        sized = name in CLUSTER_SIGNATURES or name in SUBST_VAR_SCAN_SIGNATURES or name in INDEL_VAR_SCAN_SIGNATURES
+        fn.restype = C.c_size_t if sized and name.endswith("_workspace_bytes") else C.c_int
     for name, args in SIZE_FUNCS.items():
         fn = getattr(lib, name)
         fn.argtypes = args

@@ -118,33 +118,55 @@ __global__ __launch_bounds__(256) void subst_var_delta_kernel(SubstVarArgs p) {
     }
 }
 
-__global__ __launch_bounds__(256) void subst_var_quad_kernel(SubstVarArgs p) {
+// What the quadratic form needs to know of a row of out, supplied by a row map (MAP::at(p, row), row < p.row_hi): its sequence, whether
+// it is live (a dead row is never read from the workspace and enters the MFMAs as zeros), the window count of the mutant's normaliser
+// (indel_norm) and the value a dead row stores.
+struct SvRow { long i; int live; int nk; double dead; };
+
+// substitutions: V rows per position, L positions per sequence, live l < s, the sequence's own normaliser, dead rows store +0.0
+struct SubstRowMap {
+    static __device__ __forceinline__ SvRow at(const SubstVarArgs &p, long row) {
+        const EditScanArgs &s = p.s;
+        SvRow o;
+        const long slot = row / s.win.vocab;
+        o.i = slot / s.L;
+        const int l = (int)(slot - o.i * s.L);
+        const int len = s.win.seqlen[o.i];
+        o.nk = len - s.win.conv_width + 1;
+        o.live = l < len ? 1 : 0;
+        o.dead = 0.0;
+        return o;
+    }
+};
+
+template <class MAP>
+__device__ __forceinline__ void sv_quad_body(const SubstVarArgs &p) {
     constexpr int NT = 256;
     constexpr int VPT = SV_KC * SV_CB / NT;              // panel elements staged per thread
     __shared__ __attribute__((aligned(16))) double vs[2][SV_KC * SV_VS];
     const EditScanArgs &s = p.s;
     const int lane = threadIdx.x & 63, c = lane & 15, g = lane >> 4;
     const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int nvar = p.nvar, V = s.win.vocab;
+    const int nvar = p.nvar;
     const long t0 = p.row_lo + (long)blockIdx.x * 64 + 16 * w;       // the wave's first row of out
     // ---- the lane's A row: row c of the tile
     const long ga = t0 + c;
     int live = 0;
     long ia = 0;
     int nka = 1;
+    double dead = 0.0;
     if (ga < p.row_hi) {
-        const long slot = ga / V;
-        ia = slot / s.L;
-        const int l = (int)(slot - ia * s.L);
-        const int len = s.win.seqlen[ia];
-        nka = len - s.win.conv_width + 1;
-        live = l < len ? 1 : 0;
+        const SvRow info = MAP::at(p, ga);
+        ia = info.live ? info.i : 0;
+        nka = info.nk;
+        live = info.live;
+        dead = info.dead;
     }
     // a workgroup none of whose 64 rows is live (positions past a length) stores its zeros and leaves; a wave without a live row keeps
     // staging Vm and meeting the barriers, but skips its matrix instructions (both decisions are uniform where they must be)
     if (!__syncthreads_or(live)) {
         const long row = t0 + lane;
-        if (lane < 16 && row < p.row_hi) p.out[row] = 0.0;
+        if (lane < 16 && row < p.row_hi) p.out[row] = dead;          // (lane < 16: c == lane, the row the lane looked up)
         return;
     }
     const bool wave_live = __any(live) != 0;
@@ -268,15 +290,17 @@ __global__ __launch_bounds__(256) void subst_var_quad_kernel(SubstVarArgs p) {
     du += __shfl_xor(du, 32);
     const double ra = indel_norm(s.ig.scale, s.scaling_type, nka);
     const double qa = live ? p.q[ia] : 0.0;
-    const double base = qa + (2.0 * ra) * du;            // row c's first two terms
+    const double base = live ? qa + (2.0 * ra) * du : dead;      // row c's first two terms, or what it stores as a dead row
     const double r2 = ra * ra;
     #pragma unroll
     for (int r = 0; r < 4; r++) {
         const double b = __shfl(base, g + 4 * r), rr = __shfl(r2, g + 4 * r);
         const long row = t0 + g + 4 * r;
-        if (c == 0 && row < p.row_hi) p.out[row] = live_d[r] ? b + rr * sq[r] : 0.0;
+        if (c == 0 && row < p.row_hi) p.out[row] = live_d[r] ? b + rr * sq[r] : b;
     }
 }
+
+__global__ __launch_bounds__(256) void subst_var_quad_kernel(SubstVarArgs p) { sv_quad_body<SubstRowMap>(p); }
 
 int conv_token_subst_var_scan_ok_impl(long width, long vocab, long C, long num_freqs, long nvar) {
     return edit_scan_ok(width, vocab, C, num_freqs) && nvar >= 2 && (nvar & 1) == 0 && nvar <= 2 * num_freqs && nvar <= SV_MAX_NVAR ? 1 : 0;

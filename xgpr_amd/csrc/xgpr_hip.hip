@@ -53,6 +53,7 @@ typedef enum { ncclFloat64 = 8 } ncclDataType_t;
 #include "../../include/xgpr_hip_subst_scan.h"
 #include "../../include/xgpr_hip_indel_scan.h"
 #include "../../include/xgpr_hip_subst_var_scan.h"
+#include "../../include/xgpr_hip_indel_var_scan.h"
 
 namespace {
 
@@ -75,6 +76,7 @@ namespace {
 #include "seq_input_grad.inc"
 #include "edit_scan.inc"
 #include "subst_var_scan.inc"
+#include "indel_var_scan.inc"
 #include "pool_input_grad.inc"
 #include "cluster.inc"
 
@@ -632,6 +634,24 @@ int xgpr_conv_token_subst_var_scan_f32(const uint8_t *tokens, const float *table
                                        size_t workspace_bytes, void *stream) {
     return subst_var_scan_impl(tokens, table, vm, vm_stride, u, q, out, radem, chi, seqlen_host, seqlen_dev, n, L, vocab, C, num_freqs,
                                radem_shape2, nvar, conv_width, scaling_type, fit_intercept, slab_rows, workspace, workspace_bytes, stream);
+}
+
+// ---- include/xgpr_hip_indel_var_scan.h
+int xgpr_conv_token_indel_var_scan_ok(long width, long vocab, long C, long num_freqs, long nvar) {
+    return conv_token_indel_var_scan_ok_impl(width, vocab, C, num_freqs, nvar);
+}
+size_t xgpr_conv_token_indel_var_scan_workspace_bytes(long radem_shape2, long nvar, long slab_rows) {
+    return conv_token_indel_var_scan_workspace_bytes_impl(radem_shape2, nvar, slab_rows);
+}
+int xgpr_conv_token_indel_var_scan_f32(const uint8_t *tokens, const float *table, const double *vm, long vm_stride, const double *u_del,
+                                       const double *q_del, const double *u_ins, const double *q_ins, double *out_del, double *out_ins,
+                                       const int8_t *radem, const float *chi, const int32_t *seqlen_host, const int32_t *seqlen_dev, long n,
+                                       long L, long vocab, long C, long num_freqs, long radem_shape2, long nvar, int conv_width,
+                                       int scaling_type, int fit_intercept, long slab_rows, void *workspace, size_t workspace_bytes,
+                                       void *stream) {
+    return indel_var_scan_impl(tokens, table, vm, vm_stride, u_del, q_del, u_ins, q_ins, out_del, out_ins, radem, chi, seqlen_host,
+                               seqlen_dev, n, L, vocab, C, num_freqs, radem_shape2, nvar, conv_width, scaling_type, fit_intercept, slab_rows,
+                               workspace, workspace_bytes, stream);
 }
 
 int xgpr_selftest_lane_xor(int32_t *out, void *stream) {

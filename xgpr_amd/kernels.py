@@ -827,6 +827,98 @@ class ConvSORFKernel(KernelBase):
         ins.masked_fill_((k > lens_dev[:, None])[:, :, None], 0.0)
         return dele, ins
 
+    # ---- the exact quadratic form of the predictive variance of every single-token deletion and insertion
+    def indel_variance_scan(self, batch, sequence_length, var):
+        """(deletions [n, L], insertions [n, L + 1, V]), float64 device tensors: ``z'^T var z'`` for the first
+        ``nvar = var.shape[0]`` columns z' of ``transform_x(mutant)``, for the sequence without its token at position p and for the
+        sequence with row v of the TokenBatch's table inserted before position g (g = length appends) -- what
+        ``xGPRegression.predict`` turns into the variance.  Exactly 0 for p >= length and g > length; the deletions of a sequence of
+        exactly conv_width tokens (no window left) are NaN.  An indel changes the window count and with it the k-mer normaliser:
+        the mutant's columns are b + r' delta with b the sequence's own columns rescaled by rho = r' / r (column 0 stays the
+        constant 1 under the intercept) and delta built from the about 2 conv_width - 1 windows at the edit site, so one pair of
+        HIP kernels per slab of mutants (``ext.hipConvTokenIndelVarScan``) transforms those windows of one 1024-frequency tile and
+        contracts the delta rows with ``var`` on the float64 matrix cores.  The sequences' own columns come from
+        ``fill_feature_rows`` (float32 rows, widened), rho from the host lengths in float64; any ``var`` is accepted through
+        1/2 (var + var^T) in the cross term, and an odd nvar is padded with a zero row and column.  Where
+        ``ext.conv_token_indel_var_scan_ok`` is 0 (windows of more than 1024 elements, a table the LDS image does not hold,
+        nvar > 2048) or the tokens are not contiguous the result comes from ``indel_variance_scan_composed``."""
+        xs, lengths, vm = self._var_scan_inputs(batch, sequence_length, var)
+        n, L, C = xs.shape
+        V, nvar = xs.table.shape[0], vm.shape[0]
+        npad = nvar + (nvar & 1)
+        if not (xs.is_cuda and xs.tokens.is_contiguous()
+                and ext.conv_token_indel_var_scan_ok(self.conv_width * C, V, C, self.num_freqs, npad) == 1):
+            return self._indel_var_composed(xs, lengths, vm)
+        self._check_lengths(lengths, n, L)
+        vp = torch.zeros((npad, npad), dtype=torch.float64, device=self.device)
+        vp[:nvar, :nvar] = vm
+        rows = torch.empty((n, self.num_rffs), dtype=torch.float32, device=self.device)
+        self.fill_feature_rows(xs, lengths, rows)
+        z = rows[:, :npad].to(torch.float64)
+        nk = lengths.astype(np.float64) - self.conv_width + 1
+        halves = []
+        for nkm in (np.maximum(nk - 1, 1), nk + 1):      # (nk - 1 == 0: no mutant, the outputs are NaN whatever rho is)
+            ratio = nk / nkm
+            rho = {0: np.ones_like(ratio), 1: np.sqrt(ratio), 2: ratio}[self.scaling_type]
+            b = z * torch.from_numpy(rho).to(self.device)[:, None]
+            if self.fit_intercept:
+                b[:, 0] = 1.0                            # rho 1 + (1 - rho): the constant column is not rescaled
+            bv = b @ vp.T                                # row i: var b_i
+            halves += [(0.5 * (bv + b @ vp)).contiguous(), (b * bv).sum(dim=1).contiguous()]
+        dele = torch.empty((n, L), dtype=torch.float64, device=self.device)
+        ins = torch.empty((n, L + 1, V), dtype=torch.float64, device=self.device)
+        ext.hipConvTokenIndelVarScan(xs.tokens, xs.table.contiguous(), vp, halves[0], halves[1], halves[2], halves[3], dele, ins,
+                                     self.radem_diag, self.chi_arr, lengths, self.conv_width, self.scaling_type, self.fit_intercept)
+        return dele, ins
+
+    def indel_variance_scan_composed(self, batch, sequence_length, var):
+        """The same result from existing operators, at every window width, table size and nvar: bounded slices of deletion and
+        insertion mutants are written out as token rows of L + 1 positions, ``fill_feature_rows`` makes their float32 feature rows,
+        the quadratic form of their first nvar columns with ``var`` is taken in float64 with torch, and the zeros and NaNs of the
+        contract are applied.  At most ``COMPOSED_SCAN_ELEMS`` float32 row elements are held at a time."""
+        return self._indel_var_composed(*self._var_scan_inputs(batch, sequence_length, var))
+
+    def _indel_var_composed(self, xs, lengths, vm):
+        n, L, _ = xs.shape
+        V, cw, dev, nvar = xs.table.shape[0], self.conv_width, self.device, vm.shape[0]
+        self._check_lengths(lengths, n, L)
+        tokens, lens_dev = xs.tokens.contiguous(), torch.from_numpy(lengths).to(dev).long()
+        step = max(1, self.COMPOSED_SCAN_ELEMS // self.num_rffs)
+        k = torch.arange(L + 1, device=dev)[None, :]
+
+        def quad(tok, lens):
+            rows = torch.empty((tok.shape[0], self.num_rffs), dtype=torch.float32, device=dev)
+            self.fill_feature_rows(TokenBatch(tok.contiguous(), xs.table), lens, rows)
+            xv = rows[:, :nvar].to(torch.float64)
+            return (xv * (xv @ vm.T)).sum(dim=1)
+
+        dele = torch.empty((n, L), dtype=torch.float64, device=dev)
+        flat = dele.view(-1)
+        for lo in range(0, n * L, step):
+            ids = torch.arange(lo, min(lo + step, n * L), device=dev)
+            seq, pos = ids // L, ids % L
+            pos = torch.where(lens_dev[seq] > cw, pos, L + 1)                   # (no mutant: the sequence itself, overwritten below)
+            src = (k + (k >= pos[:, None]).long()).clamp_(max=L - 1)            # position k of the mutant reads k + (k >= p)
+            mut = torch.gather(tokens[seq], 1, src)
+            mlen = (lens_dev[seq] - 1).clamp_(min=cw)                           # (entries with no mutant are overwritten below)
+            flat[lo:lo + step] = quad(mut, mlen.to(torch.int32).cpu().numpy())
+        ins = torch.empty((n, L + 1, V), dtype=torch.float64, device=dev)
+        flat = ins.view(-1)
+        for lo in range(0, n * (L + 1) * V, step):
+            ids = torch.arange(lo, min(lo + step, n * (L + 1) * V), device=dev)
+            seq, gap, tok = ids // ((L + 1) * V), (ids // V) % (L + 1), ids % V
+            src = (k - (k > gap[:, None]).long()).clamp_(max=L - 1)             # k < g reads k, k > g reads k - 1 ...
+            mut = torch.gather(tokens[seq], 1, src)
+            mut[torch.arange(ids.shape[0], device=dev), gap] = tok.to(torch.uint8)      # ... and k == g is the new token
+            mlen = lens_dev[seq] + (gap <= lens_dev[seq]).long()               # (no such gap: the sequence itself, overwritten below)
+            flat[lo:lo + step] = quad(mut, mlen.to(torch.int32).cpu().numpy())
+        # the contract's zeros (no such position or gap) and NaNs (a deletion that leaves no window)
+        pos = torch.arange(L, device=dev)[None, :]
+        dele.masked_fill_((lens_dev[:, None] == cw) & (pos < lens_dev[:, None]), float("nan"))
+        dele.masked_fill_(pos >= lens_dev[:, None], 0.0)
+        ins.masked_fill_((k > lens_dev[:, None])[:, :, None], 0.0)
+        return dele, ins
+
     def grad_rows_ok(self):
         """Whether ``fill_grad_rows`` can write this kernel's float32 feature AND gradient rows, and the exact NMLL
         gradient's accumulations can run on them (nmll.calc_gradient_terms): a HIP device -- the writer serves every

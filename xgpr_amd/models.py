@@ -290,7 +290,7 @@ class xGPRegression(_ModelBase):
             raise RuntimeError("The shape[0] of sequence_lengths must match the shape[0] of input_x.")
         return input_x, sequence_lengths
 
-    def predict_indels(self, input_x, sequence_lengths=None, token_table=None, chunk_size=64):
+    def predict_indels(self, input_x, sequence_lengths=None, token_table=None, chunk_size=64, get_var=False):
         """The exact effect of every single deletion and insertion on ``predict`` (no counterpart in the reference) -> numpy
         float64 (deletions [N, L], insertions [N, L + 1, V]): deletions[i, p] is the predicted mean of sequence i without its
         token at position p, insertions[i, g, v] that of sequence i with row v of the token table inserted before position g
@@ -299,15 +299,35 @@ class xGPRegression(_ModelBase):
         a sequence of exactly conv_width tokens, whose mutant has no k-mer.  Input and kernels as for ``predict_substitutions``.
         An indel only shifts the windows away from the edit, so the scan transforms about conv_width windows per edit plus
         the sequence's own windows once, and rescales the total by the mutant's k-mer normaliser; no mutant is written
-        (DESIGN.md 3.21).  The VARIANCE of the indel mutants is not built yet: the identity of ``predict_substitutions(get_var=True)``
-        holds there too, with the mutant's normaliser r' and the shifted window set."""
+        (DESIGN.md 3.21).  With ``get_var=True`` the return is (deletions, insertions, deletion_variances,
+        insertion_variances): the predictive VARIANCE of every such mutant as ``predict(get_var=True)`` gives it -- trainy_std^2
+        max(0, lambda^2 + lambda^2 z'^T var z') --, exactly 0 for p >= the length and g > the length and NaN where the deletions
+        are NaN.  The identity of ``predict_substitutions(get_var=True)`` holds with the mutant's normaliser r': the sequence's own
+        variance columns are rescaled by r' / r and moved by r' times a vector built from the windows at the edit site alone
+        (``ConvSORFKernel.indel_variance_scan``)."""
+        if get_var and self.weights is not None and self.var is None:
+            raise RuntimeError("Variance was requested but suppress_var was selected when fitting.")
         input_x, sequence_lengths = self._token_scan_input("predict_indels", input_x, sequence_lengths, token_table)
+        n, L, V = input_x.shape[0], input_x.shape[1], input_x.table.shape[0]
         scans = [self.kernel.indel_scan(input_x[i:i + chunk_size], sequence_lengths[i:i + chunk_size], self.weights)
-                 for i in range(0, input_x.shape[0], chunk_size)]
+                 for i in range(0, n, chunk_size)]
         if not scans:
-            return np.zeros((0, input_x.shape[1])), np.zeros((0, input_x.shape[1] + 1, input_x.table.shape[0]))
-        return (torch.cat([s[0] for s in scans]).cpu().numpy() * self.trainy_std,
-                torch.cat([s[1] for s in scans]).cpu().numpy() * self.trainy_std)
+            none = (np.zeros((0, L)), np.zeros((0, L + 1, V)))
+            return none + (np.zeros((0, L)), np.zeros((0, L + 1, V))) if get_var else none
+        means = (torch.cat([s[0] for s in scans]).cpu().numpy() * self.trainy_std,
+                 torch.cat([s[1] for s in scans]).cpu().numpy() * self.trainy_std)
+        if not get_var:
+            return means
+        lambda_ = float(self.kernel.get_lambda())
+        quads = [self.kernel.indel_variance_scan(input_x[i:i + chunk_size], sequence_lengths[i:i + chunk_size], self.var)
+                 for i in range(0, n, chunk_size)]
+        out = []
+        for half, first in ((0, L), (1, L + 1)):
+            var = lambda_ ** 2 + lambda_ ** 2 * torch.cat([q[half] for q in quads]).cpu().numpy()
+            var[var < 0] = 0                                 # (a NaN stays a NaN)
+            var[np.arange(first)[None, :] >= sequence_lengths[:, None] + half] = 0
+            out.append(var * self.trainy_std ** 2)
+        return means + tuple(out)
 
     def predict_window_scores(self, input_x, sequence_lengths=None, token_table=None, chunk_size=64):
         """The share of every k-mer window in ``predict`` (no counterpart in the reference) -> numpy float64 [N, L]: entry

@@ -1177,6 +1177,67 @@ def hipConvTokenIndelScan(tokens, table, weights, scores, deletions, insertions,
         chi.shape[0], radem.shape[2], int(conv_width), int(scaling_type), int(bool(fit_intercept)), wp, wn, _stream()))
 
 
+def conv_token_indel_var_scan_ok(width, vocab, C, num_freqs, nvar):
+    """Whether hipConvTokenIndelVarScan's kernels serve the shape: where ``conv_token_indel_scan_ok`` is 1 and ``nvar`` is even,
+    at least 2 and at most min(2 * num_freqs, 2048); no device work."""
+    return int(_LIB.xgpr_conv_token_indel_var_scan_ok(int(width), int(vocab), int(C), int(num_freqs), int(nvar)))
+
+
+def conv_token_indel_var_scan_workspace_bytes(radem_shape2, nvar, slab_rows=0):
+    """The exact workspace of hipConvTokenIndelVarScan in bytes: the packed sign masks and ``slab_rows`` float64 rows of ``nvar``
+    columns (0: the library's default)."""
+    return int(_LIB.xgpr_conv_token_indel_var_scan_workspace_bytes(int(radem_shape2), int(nvar), int(slab_rows)))
+
+
+def hipConvTokenIndelVarScan(tokens, table, vm, u_del, q_del, u_ins, q_ins, deletions, insertions, radem, chi, seqlen, conv_width,
+                             scaling_type, fit_intercept, slab_rows=0, workspace=None):
+    """``deletions[n, L]`` <- ``z'^T vm z'`` over the first ``nvar = vm.shape[0]`` feature columns z' of the sequence without its
+    token at p, and ``insertions[n, L + 1, V]`` <- the same for the sequence with table row v inserted before position g (g = length
+    appends); both float64 and OVERWRITTEN, exactly +0.0 past a sequence's length, quiet NaN for the deletions of a sequence of
+    conv_width tokens (include/xgpr_hip_indel_var_scan.h).  ``vm`` float64 [nvar, nvar] (rows may be strided; nvar even);
+    ``u_del``, ``u_ins`` [n, nvar] = 1/2 (vm + vm^T) b and ``q_del``, ``q_ins`` [n] = b^T vm b for the sequences' rescaled columns
+    b = rho z + (1 - rho) e0 with each row set's own rho, float64 and precomputed by the caller.  Either group (u, q, output) may be
+    None as a whole (that half is skipped), not both.  ``slab_rows`` mutant rows are held in the workspace at a time (0: the default
+    -- the library's, or the call's own rows where those are fewer --; otherwise a multiple of 16; the result does not depend on it).
+    Shapes for which ``conv_token_indel_var_scan_ok`` is 0 raise RuntimeError and launch nothing."""
+    t, tab = _dev(tokens, "tokens", torch.uint8, 2), _dev(table, "table", torch.float32, 2)
+    r, c = _radem3(radem), _dev(chi, "chi", torch.float32, 1)
+    n, L = tokens.shape
+    V = table.shape[0]
+    if vm.dim() != 2 or vm.dtype != torch.float64 or not vm.is_cuda or vm.shape[0] != vm.shape[1] or vm.stride(1) != 1:
+        raise RuntimeError("vm must be a float64 device matrix [nvar, nvar] with contiguous rows.")
+    nvar = vm.shape[0]
+    ptrs = []
+    for u, q, out, shape, what in ((u_del, q_del, deletions, (n, L), "deletions"), (u_ins, q_ins, insertions, (n, L + 1, V), "insertions")):
+        given = [x is not None for x in (u, q, out)]
+        if not any(given):
+            ptrs.append((None, None, None))
+            continue
+        if not all(given):
+            raise RuntimeError(f"{what}: u, q and the output are given together or not at all.")
+        ptrs.append((_dev(u, "u", torch.float64, 2), _dev(q, "q", torch.float64, 1), _dev(out, what, torch.float64, len(shape))))
+        if tuple(out.shape) != shape or tuple(u.shape) != (n, nvar) or q.shape[0] != n:
+            raise RuntimeError("Wrong array sizes.")
+    host, dev = _seqlens(seqlen, tokens.device)
+    if host.shape[0] != n:
+        raise RuntimeError("wrong array sizes")
+    if workspace is None:
+        if slab_rows == 0 and nvar >= 2 and nvar % 2 == 0:
+            # (a call with fewer mutant rows than the default slab holds allocates no more than its rows: the slab size does not enter the result)
+            masks = int(_LIB.xgpr_rbf_workspace_bytes(radem.shape[2]))
+            default = (conv_token_indel_var_scan_workspace_bytes(radem.shape[2], nvar, 0) - masks) // (8 * nvar)
+            rows = max(16, -(-n * (L + 1) * V // 16) * 16)
+            slab_rows = rows if rows < default else 0
+        ws, wp, wn = _workspace(conv_token_indel_var_scan_workspace_bytes(radem.shape[2], nvar, slab_rows), tokens.device)
+    else:
+        ws, wp, wn = workspace, C.c_void_p(workspace.data_ptr()), C.c_size_t(workspace.numel() * workspace.element_size())
+    (ud, qd, od), (ui, qi, oi) = ptrs
+    return _lib.check(_LIB.xgpr_conv_token_indel_var_scan_f32(
+        t, tab, C.c_void_p(vm.data_ptr()), vm.stride(0), ud, qd, ui, qi, od, oi, r, c, C.c_void_p(host.ctypes.data),
+        C.c_void_p(dev.data_ptr()), n, L, V, table.shape[1], chi.shape[0], radem.shape[2], nvar, int(conv_width),
+        int(scaling_type), int(bool(fit_intercept)), int(slab_rows), wp, wn, _stream()))
+
+
 def conv_maxpool_input_grad_ok(width):
     """Whether hipConvMaxpoolInputGrad's kernel serves a window of ``width`` = conv_width * C elements (padded width up to 1024)."""
     return int(_LIB.xgpr_conv_maxpool_input_grad_ok(int(width)))
