@@ -150,6 +150,11 @@ INDEL_VAR_SCAN_SIGNATURES = {
     "xgpr_conv_token_indel_var_scan_f32": [_vp, _vp, _vp, _l, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _l, _l, _l, _l, _l, _l, _l,
                                            _i, _i, _i, _l, _vp, _sz, _vp],
 }
+# ... and include/xgpr_hip_pair_scan.h, the eleventh (tests/test_pair_scan_host.py)
+PAIR_SCAN_SIGNATURES = {
+    "xgpr_conv_token_pair_scan_ok": [_l, _l, _l, _l],
+    "xgpr_conv_token_pair_scan_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _l, _l, _l, _l, _l, _l, _i, _i, _i, _vp, _sz, _vp],
+}
 STRING_FUNCS = ["xgpr_last_error", "xgpr_build_arch", "xgpr_build_id"]
 
 _lib = None
@@ -171,7 +176,8 @@ def load():
     for name, args in (list(SIGNATURES.items()) + list(POOL_SIGNATURES.items()) + list(INPUT_GRAD_SIGNATURES.items())
                        + list(SEQ_INPUT_GRAD_SIGNATURES.items()) + list(POOL_INPUT_GRAD_SIGNATURES.items()) + list(CLUSTER_SIGNATURES.items())
                        + list(SUBST_SCAN_SIGNATURES.items()) + list(INDEL_SCAN_SIGNATURES.items())
-                       + list(SUBST_VAR_SCAN_SIGNATURES.items()) + list(INDEL_VAR_SCAN_SIGNATURES.items())):
+                       + list(SUBST_VAR_SCAN_SIGNATURES.items()) + list(INDEL_VAR_SCAN_SIGNATURES.items())
+                       + list(PAIR_SCAN_SIGNATURES.items())):
         fn = getattr(lib, name)
         fn.argtypes = args
         sized = name in CLUSTER_SIGNATURES or name in SUBST_VAR_SCAN_SIGNATURES or name in INDEL_VAR_SCAN_SIGNATURES

@@ -190,10 +190,10 @@ constexpr EditScanOp SUBST_OP = {0, "the substitution scan serves windows of up 
 constexpr EditScanOp INDEL_OP = {1, "the indel scan serves windows of up to 1024 elements and tables of up to 4608 floats (see xgpr_conv_token_indel_scan_ok)",
                                  "too many positions for one launch (n * (L + 1) < 2^24)"};   // (the window scores included)
 
-// the checks of the three entry points, in the documented order; `bufs_ok`: every array the call needs is there; `outs_ok`: an output too
-int edit_scan_check(const EditScanOp &op, const int32_t *seqlen_host, long n, long L, long vocab, long C, long num_freqs, long R,
-                    int conv_width, int scaling_type, const void *workspace, size_t wbytes, bool bufs_ok, bool outs_ok, bool *launch) {
-    *launch = false;
+// the checks of the entry points, in the documented order, in two halves (the pair scan, pair_scan.inc, has an exit of its own between
+// them): the shape, down to the _ok predicate ...
+int edit_scan_shape_check(const EditScanOp &op, const int32_t *seqlen_host, long n, long L, long vocab, long C, long num_freqs, long R,
+                          int conv_width, int scaling_type) {
     if (n < 0 || L < 1 || C < 1) return fail(XGPR_ERR_ARRAY_DIMS, "incorrect array dims passed");
     if (scaling_type < 0 || scaling_type > 2) return fail(XGPR_ERR_ARRAY_DIMS, "scaling_type must be 0, 1 or 2");
     if (conv_width <= 0 || L < conv_width) return fail(XGPR_ERR_CONV_WIDTH, "invalid conv_width");
@@ -206,10 +206,22 @@ int edit_scan_check(const EditScanOp &op, const int32_t *seqlen_host, long n, lo
     }
     if (vocab < 1 || vocab > 256) return fail(XGPR_ERR_ARRAY_DIMS, "token table: vocab must be 1 .. 256 (uint8 tokens)");
     if (!edit_scan_ok(win, vocab, C, num_freqs)) return fail(XGPR_ERR_UNSUPPORTED, op.unsupported);
-    if (n == 0) return 0;
+    return 0;
+}
+// ... and, where something will be launched, the workspace and the arrays; `bufs_ok`: every array the call needs is there; `outs_ok`: an output too
+int edit_scan_buffer_check(const void *workspace, size_t wbytes, long R, bool bufs_ok, bool outs_ok) {
     if (!workspace || wbytes < masks_bytes(R)) return fail(XGPR_ERR_WORKSPACE, "workspace too small (see xgpr_rbf_workspace_bytes)");
     if (!bufs_ok) return fail(XGPR_ERR_WORKSPACE, "NULL array pointer");
     if (!outs_ok) return fail(XGPR_ERR_WORKSPACE, "NULL array pointer (del and ins are both NULL: nothing to compute)");
+    return 0;
+}
+int edit_scan_check(const EditScanOp &op, const int32_t *seqlen_host, long n, long L, long vocab, long C, long num_freqs, long R,
+                    int conv_width, int scaling_type, const void *workspace, size_t wbytes, bool bufs_ok, bool outs_ok, bool *launch) {
+    *launch = false;
+    int rc = edit_scan_shape_check(op, seqlen_host, n, L, vocab, C, num_freqs, R, conv_width, scaling_type);
+    if (rc || n == 0) return rc;
+    rc = edit_scan_buffer_check(workspace, wbytes, R, bufs_ok, outs_ok);
+    if (rc) return rc;
     if (n > 2147483647L || n * (L + op.gaps) > 16777215L) return fail(XGPR_ERR_UNSUPPORTED, op.too_many);
     *launch = true;
     return 0;

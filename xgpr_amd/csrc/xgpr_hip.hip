@@ -54,6 +54,7 @@ typedef enum { ncclFloat64 = 8 } ncclDataType_t;
 #include "../../include/xgpr_hip_indel_scan.h"
 #include "../../include/xgpr_hip_subst_var_scan.h"
 #include "../../include/xgpr_hip_indel_var_scan.h"
+#include "../../include/xgpr_hip_pair_scan.h"
 
 namespace {
 
@@ -75,6 +76,7 @@ namespace {
 #include "input_grad.inc"
 #include "seq_input_grad.inc"
 #include "edit_scan.inc"
+#include "pair_scan.inc"
 #include "subst_var_scan.inc"
 #include "indel_var_scan.inc"
 #include "pool_input_grad.inc"
@@ -652,6 +654,18 @@ int xgpr_conv_token_indel_var_scan_f32(const uint8_t *tokens, const float *table
     return indel_var_scan_impl(tokens, table, vm, vm_stride, u_del, q_del, u_ins, q_ins, out_del, out_ins, radem, chi, seqlen_host,
                                seqlen_dev, n, L, vocab, C, num_freqs, radem_shape2, nvar, conv_width, scaling_type, fit_intercept, slab_rows,
                                workspace, workspace_bytes, stream);
+}
+
+// ---- include/xgpr_hip_pair_scan.h
+int xgpr_conv_token_pair_scan_ok(long width, long vocab, long C, long num_freqs) {
+    return conv_token_pair_scan_ok_impl(width, vocab, C, num_freqs);
+}
+int xgpr_conv_token_pair_scan_f32(const uint8_t *tokens, const float *table, const double *w, double *out, const int8_t *radem,
+                                  const float *chi, const int32_t *seqlen_host, const int32_t *seqlen_dev, long n, long L, long vocab,
+                                  long C, long num_freqs, long radem_shape2, int conv_width, int scaling_type, int fit_intercept,
+                                  void *workspace, size_t workspace_bytes, void *stream) {
+    return pair_scan_impl(tokens, table, w, out, radem, chi, seqlen_host, seqlen_dev, n, L, vocab, C, num_freqs, radem_shape2,
+                          conv_width, scaling_type, fit_intercept, workspace, workspace_bytes, stream);
 }
 
 int xgpr_selftest_lane_xor(int32_t *out, void *stream) {

@@ -627,6 +627,83 @@ class ConvSORFKernel(KernelBase):
         same = (pos[None, :] >= lens_dev[:, None])[:, :, None] | (torch.arange(V, device=dev)[None, None, :] == tokens.long()[:, :, None])
         return out.masked_fill_(same, 0.0)
 
+    # ---- the exact non-additive part of every pair of substitutions closer than conv_width
+    PAIR_SCAN_ROWS = 1 << 24         # rows [V] of the output one launch serves (xgpr_conv_token_pair_scan_f32: one workgroup each)
+
+    def pair_substitution_scan(self, batch, sequence_length, weights):
+        """float64 device tensor [n, L, conv_width - 1, V, V]: entry [i, l1, d - 1, v1, v2] is ``transform_x(sequence with token
+        l1 replaced by v1 and token l1 + d by v2) @ weights`` minus ``transform_x(sequence) @ weights`` minus the two entries
+        [i, l1, v1] and [i, l1 + d, v2] of ``substitution_scan`` -- what two substitutions do together beyond what each does alone.
+        Exactly 0 where either token is the sequence's own and where either position is past its length; two substitutions
+        conv_width or more apart share no window and add exactly, so the band is the whole of it (no entry at all for the graph
+        kernels).  Only the conv_width - d windows that cover both positions are transformed, and no mutant is written
+        (``ext.hipConvTokenPairScan``); a batch of more than ``PAIR_SCAN_ROWS`` output rows goes to the operator in slices.  Where
+        ``ext.conv_token_pair_scan_ok`` is 0 (windows of more than 1024 elements, a table the LDS image does not hold) or the
+        tokens are not contiguous the result comes from ``pair_substitution_scan_composed``."""
+        xs, lengths, w = self._scan_inputs(batch, sequence_length, weights)
+        n, L, _ = xs.shape
+        V, band = xs.table.shape[0], self.conv_width - 1
+        if not self._scan_operator_ok(xs, ext.conv_token_pair_scan_ok):
+            return self._pair_scan_composed(xs, lengths, w)
+        out = torch.empty((n, L, band, V, V), dtype=torch.float64, device=self.device)
+        table = xs.table.contiguous()
+        step = max(1, (self.PAIR_SCAN_ROWS - 1) // max(1, L * band * V))
+        for lo in range(0, max(n, 1), step):             # (n == 0: one call, for its checks)
+            ext.hipConvTokenPairScan(xs.tokens[lo:lo + step], table, w, out[lo:lo + step], self.radem_diag, self.chi_arr,
+                                     lengths[lo:lo + step], self.conv_width, self.scaling_type, self.fit_intercept)
+        return out
+
+    def pair_substitution_scan_composed(self, batch, sequence_length, weights):
+        """The same result from existing operators, at every window width and table size: bounded slices of written-out single
+        and double mutants go through ``fill_feature_rows`` and ``hipZCacheBlockProject`` with one column, and an entry is
+        ``(m(both) - m(v1 alone)) - (m(v2 alone) - m(sequence))``.  Only the slots inside a sequence are written out; the own-token
+        planes and the slots past a length are set to exact zeros.  At most ``COMPOSED_SCAN_ELEMS`` float32 row elements are
+        held at a time."""
+        return self._pair_scan_composed(*self._scan_inputs(batch, sequence_length, weights))
+
+    def _pair_scan_composed(self, xs, lengths, w):
+        n, L, _ = xs.shape
+        V, dev, band = xs.table.shape[0], self.device, self.conv_width - 1
+        self._check_lengths(lengths, n, L)
+        out = torch.zeros((n, L, band, V, V), dtype=torch.float64, device=dev)
+        if out.numel() == 0:
+            return out
+        project = self._projector(xs.table, w)
+        tokens, lens_dev = xs.tokens.contiguous(), torch.from_numpy(lengths).to(dev)
+        step = max(1, self.COMPOSED_SCAN_ELEMS // self.num_rffs)
+
+        def mutants(seq, edits):
+            mut = tokens[seq]
+            rows = torch.arange(seq.shape[0], device=dev)
+            for pos, tok in edits:
+                mut[rows, pos] = tok.to(torch.uint8)
+            return project(mut, lengths[seq.cpu().numpy()])
+
+        base = torch.empty(n, dtype=torch.float64, device=dev)
+        for lo in range(0, n, step):
+            base[lo:lo + step] = project(tokens[lo:lo + step], lengths[lo:lo + step])
+        pos = torch.arange(L, device=dev)
+        # m of every single mutant inside a sequence, once: [n, L, V]
+        single = torch.zeros((n, L, V), dtype=torch.float64, device=dev)
+        slots = (pos[None, :] < lens_dev[:, None]).nonzero()
+        for lo in range(0, slots.shape[0] * V, step):
+            ids = torch.arange(lo, min(lo + step, slots.shape[0] * V), device=dev)
+            (seq, l), v = slots[ids // V].T, ids % V
+            single[seq, l, v] = mutants(seq, [(l, v)])
+        # ... and of every double mutant with both positions inside it
+        second = pos[:, None] + 1 + torch.arange(band, device=dev)[None, :]              # [L, band]: l2 of slot (l1, d - 1)
+        slots = (second[None, :, :] < lens_dev[:, None, None]).nonzero()
+        for lo in range(0, slots.shape[0] * V * V, step):
+            ids = torch.arange(lo, min(lo + step, slots.shape[0] * V * V), device=dev)
+            (seq, l1, dd), v1, v2 = slots[ids // (V * V)].T, (ids // V) % V, ids % V
+            l2 = l1 + dd + 1
+            out[seq, l1, dd, v1, v2] = (mutants(seq, [(l1, v1), (l2, v2)]) - single[seq, l1, v1]) - (single[seq, l2, v2] - base[seq])
+        # either token the sequence's own: the double mutant is a single one
+        own = tokens.long()
+        tok = torch.arange(V, device=dev)
+        out.masked_fill_((tok[None, None, :] == own[:, :, None])[:, :, None, :, None], 0.0)
+        return out.masked_fill_((tok[None, None, None, :] == own[:, second.clamp(max=L - 1)][:, :, :, None])[:, :, :, None, :], 0.0)
+
     # ---- the exact quadratic form of the predictive variance of every single-token substitution (DESIGN.md 3.22)
     def _var_scan_inputs(self, batch, sequence_length, var):
         if not isinstance(batch, TokenBatch):

@@ -290,6 +290,29 @@ class xGPRegression(_ModelBase):
             raise RuntimeError("The shape[0] of sequence_lengths must match the shape[0] of input_x.")
         return input_x, sequence_lengths
 
+    def predict_substitution_pairs(self, input_x, sequence_lengths=None, token_table=None, chunk_size=4):
+        """The exact non-additive part (epistasis) of every pair of substitutions closer than conv_width (no counterpart in the
+        reference) -> numpy float64 [N, L, conv_width - 1, V, V], in the units of y (times the training y's standard deviation).
+        With ``sub = predict_substitutions(...)`` and ``pairs`` this result, the predicted mean of sequence i with its token at
+        l1 replaced by v1 and its token at l2 = l1 + d replaced by v2 is
+
+            mean(double) = predict + sub[i, l1, v1] + sub[i, l2, v2] + (pairs[i, l1, d - 1, v1, v2] if d < conv_width else 0)
+
+        exactly: the feature row is a sum over k-mer windows, only the conv_width - d windows that cover both positions see both
+        substitutions, and two positions conv_width or more apart share none (for the graph kernels the third axis is empty).
+        Exactly 0 where either token is the sequence's own and where either position is past the sequence's length.  Input,
+        kernels and refusals as for ``predict_substitutions``.  One HIP kernel transforms the shared windows alone and writes no
+        mutant (``ConvSORFKernel.pair_substitution_scan``).  The output is large -- 14.5 MB per sequence of a
+        512-position array at conv_width 9 and V = 21 --, which is why ``chunk_size``, the sequences that go to the device at a
+        time, is small."""
+        input_x, sequence_lengths = self._token_scan_input("predict_substitution_pairs", input_x, sequence_lengths, token_table)
+        n, L, V = input_x.shape[0], input_x.shape[1], input_x.table.shape[0]
+        out = np.zeros((n, L, self.kernel.conv_width - 1, V, V))
+        for i in range(0, n, chunk_size):
+            scan = self.kernel.pair_substitution_scan(input_x[i:i + chunk_size], sequence_lengths[i:i + chunk_size], self.weights)
+            out[i:i + chunk_size] = scan.cpu().numpy() * self.trainy_std
+        return out
+
     def predict_indels(self, input_x, sequence_lengths=None, token_table=None, chunk_size=64, get_var=False):
         """The exact effect of every single deletion and insertion on ``predict`` (no counterpart in the reference) -> numpy
         float64 (deletions [N, L], insertions [N, L + 1, V]): deletions[i, p] is the predicted mean of sequence i without its

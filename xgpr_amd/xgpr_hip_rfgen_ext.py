@@ -1085,6 +1085,31 @@ def hipConvTokenSubstScan(tokens, table, weights, out, radem, chi, seqlen, conv_
         chi.shape[0], radem.shape[2], int(conv_width), int(scaling_type), int(bool(fit_intercept)), wp, wn, _stream()))
 
 
+def conv_token_pair_scan_ok(width, vocab, C, num_freqs):
+    """Whether hipConvTokenPairScan's kernels serve a window of ``width`` = conv_width * C elements over a table of ``vocab`` rows
+    and ``C`` columns (where ``conv_token_subst_scan_ok`` is 1); no device work."""
+    return int(_LIB.xgpr_conv_token_pair_scan_ok(int(width), int(vocab), int(C), int(num_freqs)))
+
+
+def hipConvTokenPairScan(tokens, table, weights, out, radem, chi, seqlen, conv_width, scaling_type, fit_intercept, workspace=None):
+    """``out[n, L, conv_width - 1, V, V]`` (float64, OVERWRITTEN) <- the non-additive part of every pair of substitutions closer
+    than conv_width: ``out[i, l1, d - 1, v1, v2]`` is ``features(sequence with token l1 replaced by v1 and token l1 + d by v2) @
+    weights`` minus ``features(sequence) @ weights`` minus the two single effects of hipConvTokenSubstScan
+    (include/xgpr_hip_pair_scan.h): exactly +0.0 where either token is the sequence's own and where either position is past its
+    length.  Operands as for hipConvTokenSubstScan.  With conv_width 1 ``out`` has no elements and nothing is launched.  Shapes
+    for which ``conv_token_pair_scan_ok`` is 0, and batches with n * L * (conv_width - 1) * V >= 2^24, raise RuntimeError and launch
+    nothing."""
+    (t, tab, w, r, c), host, dev, ws, wp, wn = _scan_operands(tokens, table, weights, radem, chi, seqlen, workspace)
+    g = _dev(out, "out", torch.float64, 5)
+    n, L = tokens.shape
+    V = table.shape[0]
+    if tuple(out.shape) != (n, L, int(conv_width) - 1, V, V):
+        raise RuntimeError("Wrong array sizes.")
+    return _lib.check(_LIB.xgpr_conv_token_pair_scan_f32(
+        t, tab, w, g, r, c, C.c_void_p(host.ctypes.data), C.c_void_p(dev.data_ptr()), n, L, V, table.shape[1],
+        chi.shape[0], radem.shape[2], int(conv_width), int(scaling_type), int(bool(fit_intercept)), wp, wn, _stream()))
+
+
 def conv_token_subst_var_scan_ok(width, vocab, C, num_freqs, nvar):
     """Whether hipConvTokenSubstVarScan's kernels serve the shape: where ``conv_token_subst_scan_ok`` is 1 and ``nvar`` is even,
     at least 2 and at most min(2 * num_freqs, 2048); no device work."""
