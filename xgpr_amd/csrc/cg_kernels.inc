@@ -414,8 +414,9 @@ __global__ __launch_bounds__(256) void precond_utr_kernel(const double *__restri
     const long rows_per = (M + gridDim.x - 1) / gridDim.x;
     const long i0 = (long)blockIdx.x * rows_per;
     const long i1 = i0 + rows_per < M ? i0 + rows_per : M;
-    if ((rank & 1) == 0) {
-        // two adjacent columns per thread (16-byte loads); rows in order, so the sums do not depend on the path
+    if ((rank & 1) == 0 && (reinterpret_cast<uintptr_t>(u) & 15) == 0) {
+        // two adjacent columns per thread (16-byte loads: u 16-byte aligned, as every row is then; part is, the launcher
+        // checks the workspace); rows in order, so the sums do not depend on the path
         for (long j = 2 * threadIdx.x; j < rank; j += 2 * blockDim.x) {
             double a0 = 0.0, a1 = 0.0;
             #pragma unroll 8
