@@ -3,7 +3,7 @@ through the comparison the GPU test uses, agrees with the contract's three-term 
 largest |Q - q~| of every case the GPU test runs, for the deletions and for the insertions; the tenth public header,
 include/xgpr_hip_indel_var_scan.h, held to what tests/test_subst_var_scan_host.py holds the ninth; the launcher's argument validation
 through the C ABI (nothing reaches a HIP call: device pointers are dummy integers); the shape predicate and the workspace size on
-the host; the recorded digests of the substitution variance scan name every case.  (The compiler's resource report of the new
+the host; the recorded digests of both variance scans name every case, and the indel file's operands are the ones built here.  (The compiler's resource report of the new
 kernels -- no scratch, no spilled vector register -- is held by tests/test_resource_usage.py, which walks every kernel.)"""
 import ctypes
 import inspect
@@ -11,6 +11,7 @@ import json
 import os
 import re
 import shutil
+import sys
 
 import numpy as np
 import pytest
@@ -23,6 +24,7 @@ from test_cabi import _build_module
 from test_subst_var_scan_host import _codes
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
 HEADER = os.path.join(ROOT, "include", "xgpr_hip_indel_var_scan.h")
 NAMES = ["xgpr_conv_token_indel_var_scan_f32", "xgpr_conv_token_indel_var_scan_ok", "xgpr_conv_token_indel_var_scan_workspace_bytes"]
 CASE_NAMES = [c[0] for c in div.CASES]
@@ -139,6 +141,42 @@ def test_the_recorded_digests_name_every_case():
         assert set(entry["inputs"]) == {"tokens", "table", "seqlen", "radem", "chi", "vm", "u64", "q64"}
 
 
+@pytest.fixture(scope="module")
+def indel_digests():
+    with open(os.path.join(ROOT, "tests", "golden", "indel_var_scan_digests.json")) as f:
+        return json.load(f)
+
+
+def test_the_indel_digests_name_every_case_and_output(indel_digests):
+    """tests/golden/indel_var_scan_digests.json (tools/var_scan_digests.py --op indel, recorded on the parent of the commit that merged
+    the two variance scans into var_scan.inc): one entry per case of dense_indel_var_scan.CASES, both outputs of one call each."""
+    import var_scan_digests as vsd
+    assert re.fullmatch(r"[0-9a-f]{40}", indel_digests["commit"])
+    assert list(indel_digests["cases"]) == vsd.INDEL_NAMES == CASE_NAMES and len(CASE_NAMES) == 12
+    for name, entry in indel_digests["cases"].items():
+        assert set(entry["outputs"]) == set(vsd.INDEL_OUTPUTS) == {"del", "ins"}, name
+        assert all(re.fullmatch(r"[0-9a-f]{64}", d) for d in entry["outputs"].values()), name
+        assert set(entry["inputs"]) == set(vsd.ARRAYS + vsd.INDEL_DERIVED), name
+
+
+@pytest.mark.parametrize("name", CASE_NAMES)
+def test_the_recorded_operands_are_the_ones_built_here(indel_digests, name):
+    """... so a mismatch of output digests on the device (tests/test_gpu_subst_var_scan_bits.py) cannot be blamed on the operands."""
+    import var_scan_digests as vsd
+    assert vsd.indel_input_digests(name) == indel_digests["cases"][name]["inputs"]
+    assert vsd.indel_first_difference(indel_digests, name) is None
+
+
+def test_a_changed_operand_is_reported_as_such(indel_digests):
+    import var_scan_digests as vsd
+    other = json.loads(json.dumps(indel_digests))
+    other["cases"]["n1"]["inputs"]["u_ins"] = "0" * 64
+    assert "operands differ (u_ins)" in vsd.indel_first_difference(other, "n1")
+    ok = dict(indel_digests["cases"]["n1"]["outputs"])
+    assert vsd.indel_first_difference(indel_digests, "n1", ok) is None
+    assert vsd.indel_first_difference(indel_digests, "n1", dict(ok, ins="0" * 64)) == "n1: output ins differs from the recorded bits"
+
+
 # ------------------------------------------------------------------------------------------------ 2. the tenth header
 def _declared():
     hdr = open(HEADER).read()
@@ -202,7 +240,7 @@ def test_every_writer_has_a_memory_contract_row():
 def test_source_id_covers_the_header_and_the_kernels(tmp_path, monkeypatch):
     bm = _build_module()
     assert os.path.samefile(bm.INDEL_VAR_SCAN_HDR, HEADER) and bm.INDEL_VAR_SCAN_HDR in bm.sources()
-    assert "indel_var_scan.inc" in [os.path.basename(p) for p in bm.sources()]
+    assert "var_scan.inc" in [os.path.basename(p) for p in bm.sources()]
     before = bm.source_id()
     copy = tmp_path / "xgpr_hip_indel_var_scan.h"
     shutil.copyfile(HEADER, copy)

@@ -31,7 +31,7 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 from bench_subst_scan import CONV_WIDTH, L, M, MIN_LEN, V, peak_bytes, timed      # noqa: E402  (the mean scan's shapes and timers)
 from bench_subst_var_scan import GRAM_TFLOPS, NVARS, mean_scan_rate, seeded_vm     # noqa: E402
 
-KERNELS = ("indel_var_delta_kernel", "indel_var_del_quad_kernel", "indel_var_ins_quad_kernel", "pack_masks")
+KERNELS = ("var_delta_kernel", "var_quad_kernel", "pack_masks")
 
 
 def tile_transforms(lengths):
@@ -55,8 +55,8 @@ def tile_transforms(lengths):
 
 
 def kernel_split(fn):
-    """{kernel name: device milliseconds} over one call, from torch.profiler (the delta kernel's two modes told apart by their template
-    argument where the profiler prints it); None where the profiler reports no device time."""
+    """{kernel name: device milliseconds} over one call, from torch.profiler (the two row sets of either kernel told apart by their
+    template argument -- the mode, the row map -- where the profiler prints it); None where the profiler reports no device time."""
     try:
         from torch.profiler import ProfilerActivity, profile
         with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
@@ -70,8 +70,10 @@ def kernel_split(fn):
             for key in KERNELS:
                 if key in ev.key and dur:
                     name = key
-                    if key == "indel_var_delta_kernel":
+                    if key == "var_delta_kernel":
                         name += " (deletions)" if ", 1>" in ev.key else " (insertions)" if ", 2>" in ev.key else ""
+                    elif key == "var_quad_kernel":
+                        name += " (deletions)" if "DelRowMap" in ev.key else " (insertions)" if "InsRowMap" in ev.key else ""
                     split[name] = split.get(name, 0.0) + dur / 1000.0
         return split or None
     except Exception as exc:                              # the profiler is an aid: the timings above do not depend on it

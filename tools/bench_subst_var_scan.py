@@ -80,7 +80,7 @@ def kernel_split(fn):
             dur = getattr(ev, "device_time_total", None)
             if dur is None:
                 dur = getattr(ev, "cuda_time_total", 0.0)
-            for key in ("subst_var_delta_kernel", "subst_var_quad_kernel", "pack_masks"):
+            for key in ("subst_var_delta_kernel", "var_quad_kernel", "pack_masks"):
                 if key in ev.key and dur:
                     split[key] = split.get(key, 0.0) + dur / 1000.0
         return split or None

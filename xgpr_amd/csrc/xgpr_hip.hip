@@ -77,8 +77,7 @@ namespace {
 #include "seq_input_grad.inc"
 #include "edit_scan.inc"
 #include "pair_scan.inc"
-#include "subst_var_scan.inc"
-#include "indel_var_scan.inc"
+#include "var_scan.inc"
 #include "pool_input_grad.inc"
 #include "cluster.inc"
 
@@ -624,10 +623,10 @@ int xgpr_conv_token_indel_scan_f32(const uint8_t *tokens, const float *table, co
 
 // ---- include/xgpr_hip_subst_var_scan.h
 int xgpr_conv_token_subst_var_scan_ok(long width, long vocab, long C, long num_freqs, long nvar) {
-    return conv_token_subst_var_scan_ok_impl(width, vocab, C, num_freqs, nvar);
+    return var_scan_ok(width, vocab, C, num_freqs, nvar);
 }
 size_t xgpr_conv_token_subst_var_scan_workspace_bytes(long radem_shape2, long nvar, long slab_rows) {
-    return conv_token_subst_var_scan_workspace_bytes_impl(radem_shape2, nvar, slab_rows);
+    return var_scan_workspace_bytes_impl(radem_shape2, nvar, slab_rows);
 }
 int xgpr_conv_token_subst_var_scan_f32(const uint8_t *tokens, const float *table, const double *vm, long vm_stride, const double *u,
                                        const double *q, double *out, const int8_t *radem, const float *chi, const int32_t *seqlen_host,
@@ -640,10 +639,10 @@ int xgpr_conv_token_subst_var_scan_f32(const uint8_t *tokens, const float *table
 
 // ---- include/xgpr_hip_indel_var_scan.h
 int xgpr_conv_token_indel_var_scan_ok(long width, long vocab, long C, long num_freqs, long nvar) {
-    return conv_token_indel_var_scan_ok_impl(width, vocab, C, num_freqs, nvar);
+    return var_scan_ok(width, vocab, C, num_freqs, nvar);
 }
 size_t xgpr_conv_token_indel_var_scan_workspace_bytes(long radem_shape2, long nvar, long slab_rows) {
-    return conv_token_indel_var_scan_workspace_bytes_impl(radem_shape2, nvar, slab_rows);
+    return var_scan_workspace_bytes_impl(radem_shape2, nvar, slab_rows);
 }
 int xgpr_conv_token_indel_var_scan_f32(const uint8_t *tokens, const float *table, const double *vm, long vm_stride, const double *u_del,
                                        const double *q_del, const double *u_ins, const double *q_ins, double *out_del, double *out_ins,

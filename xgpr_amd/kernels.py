@@ -718,6 +718,23 @@ class ConvSORFKernel(KernelBase):
             raise RuntimeError("var must be a square matrix over the first 1 .. num_rffs feature columns.")
         return xs, lengths, vm
 
+    def _var_scan_columns(self, xs, lengths, vm, ok, check_lengths=False):
+        """What the two variance scans feed their operator from -> (``var`` padded with a zero row and column to an even size, the
+        sequences' own first columns: float32 rows of ``fill_feature_rows``, widened), or None where the operator's predicate ``ok``
+        is 0 or the tokens are not contiguous: the composed route.  ``check_lengths``: hold the lengths to the array on this route."""
+        n, L, C = xs.shape
+        V, nvar = xs.table.shape[0], vm.shape[0]
+        npad = nvar + (nvar & 1)
+        if not (xs.is_cuda and xs.tokens.is_contiguous() and ok(self.conv_width * C, V, C, self.num_freqs, npad) == 1):
+            return None
+        if check_lengths:
+            self._check_lengths(lengths, n, L)
+        vp = torch.zeros((npad, npad), dtype=torch.float64, device=self.device)
+        vp[:nvar, :nvar] = vm
+        rows = torch.empty((n, self.num_rffs), dtype=torch.float32, device=self.device)
+        self.fill_feature_rows(xs, lengths, rows)
+        return vp, rows[:, :npad].to(torch.float64)
+
     def substitution_variance_scan(self, batch, sequence_length, var):
         """float64 device tensor [n, L, V]: ``z'^T var z'`` for the first ``nvar = var.shape[0]`` columns z' of
         ``transform_x(sequence with token l replaced by v)``, for every position l and every row v of the TokenBatch's table --
@@ -730,17 +747,12 @@ class ConvSORFKernel(KernelBase):
         1024 elements, a table the LDS image does not hold, nvar > 2048) or the tokens are not contiguous the result comes from
         ``substitution_variance_scan_composed``."""
         xs, lengths, vm = self._var_scan_inputs(batch, sequence_length, var)
-        n, L, C = xs.shape
-        V, nvar = xs.table.shape[0], vm.shape[0]
-        npad = nvar + (nvar & 1)
-        if not (xs.is_cuda and xs.tokens.is_contiguous()
-                and ext.conv_token_subst_var_scan_ok(self.conv_width * C, V, C, self.num_freqs, npad) == 1):
+        n, L, _ = xs.shape
+        V = xs.table.shape[0]
+        columns = self._var_scan_columns(xs, lengths, vm, ext.conv_token_subst_var_scan_ok)
+        if columns is None:
             return self._var_scan_composed(xs, lengths, vm)
-        vp = torch.zeros((npad, npad), dtype=torch.float64, device=self.device)
-        vp[:nvar, :nvar] = vm
-        rows = torch.empty((n, self.num_rffs), dtype=torch.float32, device=self.device)
-        self.fill_feature_rows(xs, lengths, rows)
-        z = rows[:, :npad].to(torch.float64)
+        vp, z = columns
         zv = z @ vp.T                                    # row i: var z_i
         u = (0.5 * (zv + z @ vp)).contiguous()           # (= var z_i for a symmetric var; the cross terms of any var)
         q = (z * zv).sum(dim=1).contiguous()
@@ -920,18 +932,12 @@ class ConvSORFKernel(KernelBase):
         ``ext.conv_token_indel_var_scan_ok`` is 0 (windows of more than 1024 elements, a table the LDS image does not hold,
         nvar > 2048) or the tokens are not contiguous the result comes from ``indel_variance_scan_composed``."""
         xs, lengths, vm = self._var_scan_inputs(batch, sequence_length, var)
-        n, L, C = xs.shape
-        V, nvar = xs.table.shape[0], vm.shape[0]
-        npad = nvar + (nvar & 1)
-        if not (xs.is_cuda and xs.tokens.is_contiguous()
-                and ext.conv_token_indel_var_scan_ok(self.conv_width * C, V, C, self.num_freqs, npad) == 1):
+        n, L, _ = xs.shape
+        V = xs.table.shape[0]
+        columns = self._var_scan_columns(xs, lengths, vm, ext.conv_token_indel_var_scan_ok, check_lengths=True)
+        if columns is None:
             return self._indel_var_composed(xs, lengths, vm)
-        self._check_lengths(lengths, n, L)
-        vp = torch.zeros((npad, npad), dtype=torch.float64, device=self.device)
-        vp[:nvar, :nvar] = vm
-        rows = torch.empty((n, self.num_rffs), dtype=torch.float32, device=self.device)
-        self.fill_feature_rows(xs, lengths, rows)
-        z = rows[:, :npad].to(torch.float64)
+        vp, z = columns
         nk = lengths.astype(np.float64) - self.conv_width + 1
         halves = []
         for nkm in (np.maximum(nk - 1, 1), nk + 1):      # (nk - 1 == 0: no mutant, the outputs are NaN whatever rho is)

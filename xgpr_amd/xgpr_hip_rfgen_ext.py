@@ -1110,6 +1110,32 @@ def hipConvTokenPairScan(tokens, table, weights, out, radem, chi, seqlen, conv_w
         chi.shape[0], radem.shape[2], int(conv_width), int(scaling_type), int(bool(fit_intercept)), wp, wn, _stream()))
 
 
+def _var_scan_nvar(vm):
+    """``vm`` of hipConvTokenSubstVarScan and hipConvTokenIndelVarScan, checked: -> nvar."""
+    if vm.dim() != 2 or vm.dtype != torch.float64 or not vm.is_cuda or vm.shape[0] != vm.shape[1] or vm.stride(1) != 1:
+        raise RuntimeError("vm must be a float64 device matrix [nvar, nvar] with contiguous rows.")
+    return vm.shape[0]
+
+
+def _var_scan_workspace(tokens, radem, seqlen, nvar, mutants, slab_rows, workspace, workspace_bytes):
+    """The host lengths, the slab and the workspace of a variance scan whose largest row set has ``mutants`` rows
+    (``workspace_bytes``: the operator's own function): -> (host, dev, slab_rows, ws, wp, wn)."""
+    host, dev = _seqlens(seqlen, tokens.device)
+    if host.shape[0] != tokens.shape[0]:
+        raise RuntimeError("wrong array sizes")
+    if workspace is None:
+        if slab_rows == 0 and nvar >= 2 and nvar % 2 == 0:
+            # (a call with fewer mutant rows than the default slab holds allocates no more than its rows: the slab size does not enter the result)
+            masks = int(_LIB.xgpr_rbf_workspace_bytes(radem.shape[2]))
+            default = (workspace_bytes(radem.shape[2], nvar, 0) - masks) // (8 * nvar)
+            rows = max(16, -(-mutants // 16) * 16)
+            slab_rows = rows if rows < default else 0
+        ws, wp, wn = _workspace(workspace_bytes(radem.shape[2], nvar, slab_rows), tokens.device)
+    else:
+        ws, wp, wn = workspace, C.c_void_p(workspace.data_ptr()), C.c_size_t(workspace.numel() * workspace.element_size())
+    return host, dev, slab_rows, ws, wp, wn
+
+
 def conv_token_subst_var_scan_ok(width, vocab, C, num_freqs, nvar):
     """Whether hipConvTokenSubstVarScan's kernels serve the shape: where ``conv_token_subst_scan_ok`` is 1 and ``nvar`` is even,
     at least 2 and at most min(2 * num_freqs, 2048); no device work."""
@@ -1135,25 +1161,12 @@ def hipConvTokenSubstVarScan(tokens, table, vm, u, q, out, radem, chi, seqlen, c
     r, c = _radem3(radem), _dev(chi, "chi", torch.float32, 1)
     g = _dev(out, "out", torch.float64, 3)
     n, L = tokens.shape
-    if vm.dim() != 2 or vm.dtype != torch.float64 or not vm.is_cuda or vm.shape[0] != vm.shape[1] or vm.stride(1) != 1:
-        raise RuntimeError("vm must be a float64 device matrix [nvar, nvar] with contiguous rows.")
-    nvar = vm.shape[0]
+    nvar = _var_scan_nvar(vm)
     uu, qq = _dev(u, "u", torch.float64, 2), _dev(q, "q", torch.float64, 1)
     if tuple(out.shape) != (n, L, table.shape[0]) or tuple(u.shape) != (n, nvar) or q.shape[0] != n:
         raise RuntimeError("Wrong array sizes.")
-    host, dev = _seqlens(seqlen, tokens.device)
-    if host.shape[0] != n:
-        raise RuntimeError("wrong array sizes")
-    if workspace is None:
-        if slab_rows == 0 and nvar >= 2 and nvar % 2 == 0:
-            # (a call with fewer mutant rows than the default slab holds allocates no more than its rows: the slab size does not enter the result)
-            masks = int(_LIB.xgpr_rbf_workspace_bytes(radem.shape[2]))
-            default = (conv_token_subst_var_scan_workspace_bytes(radem.shape[2], nvar, 0) - masks) // (8 * nvar)
-            rows = max(16, -(-n * L * table.shape[0] // 16) * 16)
-            slab_rows = rows if rows < default else 0
-        ws, wp, wn = _workspace(conv_token_subst_var_scan_workspace_bytes(radem.shape[2], nvar, slab_rows), tokens.device)
-    else:
-        ws, wp, wn = workspace, C.c_void_p(workspace.data_ptr()), C.c_size_t(workspace.numel() * workspace.element_size())
+    host, dev, slab_rows, ws, wp, wn = _var_scan_workspace(tokens, radem, seqlen, nvar, n * L * table.shape[0], slab_rows, workspace,
+                                                           conv_token_subst_var_scan_workspace_bytes)
     return _lib.check(_LIB.xgpr_conv_token_subst_var_scan_f32(
         t, tab, C.c_void_p(vm.data_ptr()), vm.stride(0), uu, qq, g, r, c, C.c_void_p(host.ctypes.data),
         C.c_void_p(dev.data_ptr()), n, L, table.shape[0], table.shape[1], chi.shape[0], radem.shape[2], nvar, int(conv_width),
@@ -1229,9 +1242,7 @@ def hipConvTokenIndelVarScan(tokens, table, vm, u_del, q_del, u_ins, q_ins, dele
     r, c = _radem3(radem), _dev(chi, "chi", torch.float32, 1)
     n, L = tokens.shape
     V = table.shape[0]
-    if vm.dim() != 2 or vm.dtype != torch.float64 or not vm.is_cuda or vm.shape[0] != vm.shape[1] or vm.stride(1) != 1:
-        raise RuntimeError("vm must be a float64 device matrix [nvar, nvar] with contiguous rows.")
-    nvar = vm.shape[0]
+    nvar = _var_scan_nvar(vm)
     ptrs = []
     for u, q, out, shape, what in ((u_del, q_del, deletions, (n, L), "deletions"), (u_ins, q_ins, insertions, (n, L + 1, V), "insertions")):
         given = [x is not None for x in (u, q, out)]
@@ -1243,19 +1254,8 @@ def hipConvTokenIndelVarScan(tokens, table, vm, u_del, q_del, u_ins, q_ins, dele
         ptrs.append((_dev(u, "u", torch.float64, 2), _dev(q, "q", torch.float64, 1), _dev(out, what, torch.float64, len(shape))))
         if tuple(out.shape) != shape or tuple(u.shape) != (n, nvar) or q.shape[0] != n:
             raise RuntimeError("Wrong array sizes.")
-    host, dev = _seqlens(seqlen, tokens.device)
-    if host.shape[0] != n:
-        raise RuntimeError("wrong array sizes")
-    if workspace is None:
-        if slab_rows == 0 and nvar >= 2 and nvar % 2 == 0:
-            # (a call with fewer mutant rows than the default slab holds allocates no more than its rows: the slab size does not enter the result)
-            masks = int(_LIB.xgpr_rbf_workspace_bytes(radem.shape[2]))
-            default = (conv_token_indel_var_scan_workspace_bytes(radem.shape[2], nvar, 0) - masks) // (8 * nvar)
-            rows = max(16, -(-n * (L + 1) * V // 16) * 16)
-            slab_rows = rows if rows < default else 0
-        ws, wp, wn = _workspace(conv_token_indel_var_scan_workspace_bytes(radem.shape[2], nvar, slab_rows), tokens.device)
-    else:
-        ws, wp, wn = workspace, C.c_void_p(workspace.data_ptr()), C.c_size_t(workspace.numel() * workspace.element_size())
+    host, dev, slab_rows, ws, wp, wn = _var_scan_workspace(tokens, radem, seqlen, nvar, n * (L + 1) * V, slab_rows, workspace,
+                                                           conv_token_indel_var_scan_workspace_bytes)
     (ud, qd, od), (ui, qi, oi) = ptrs
     return _lib.check(_LIB.xgpr_conv_token_indel_var_scan_f32(
         t, tab, C.c_void_p(vm.data_ptr()), vm.stride(0), ud, qd, ui, qi, od, oi, r, c, C.c_void_p(host.ctypes.data),
