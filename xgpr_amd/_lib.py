@@ -155,6 +155,14 @@ PAIR_SCAN_SIGNATURES = {
     "xgpr_conv_token_pair_scan_ok": [_l, _l, _l, _l],
     "xgpr_conv_token_pair_scan_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _l, _l, _l, _l, _l, _l, _i, _i, _i, _vp, _sz, _vp],
 }
+# ... and include/xgpr_hip/pool_edits.h, the twelfth (tests/test_pool_edits_host.py); why its name does not end like the others': see
+# that header's opening comment
+POOL_EDITS_ABI = {
+    "xgpr_conv_token_maxpool_edits_ok": [_l, _l, _l, _l],
+    "xgpr_conv_token_maxpool_tables_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _l, _l, _l, _l, _l, _l, _l, _i, _vp, _sz, _vp],
+    "xgpr_conv_token_maxpool_edits_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _l, _l, _l, _l, _l, _l, _l, _i, _i, _l, _l, _vp,
+                                          _sz, _vp],
+}
 STRING_FUNCS = ["xgpr_last_error", "xgpr_build_arch", "xgpr_build_id"]
 
 _lib = None
@@ -177,7 +185,7 @@ def load():
                        + list(SEQ_INPUT_GRAD_SIGNATURES.items()) + list(POOL_INPUT_GRAD_SIGNATURES.items()) + list(CLUSTER_SIGNATURES.items())
                        + list(SUBST_SCAN_SIGNATURES.items()) + list(INDEL_SCAN_SIGNATURES.items())
                        + list(SUBST_VAR_SCAN_SIGNATURES.items()) + list(INDEL_VAR_SCAN_SIGNATURES.items())
-                       + list(PAIR_SCAN_SIGNATURES.items())):
+                       + list(PAIR_SCAN_SIGNATURES.items()) + list(POOL_EDITS_ABI.items())):
         fn = getattr(lib, name)
         fn.argtypes = args
         sized = name in CLUSTER_SIGNATURES or name in SUBST_VAR_SCAN_SIGNATURES or name in INDEL_VAR_SCAN_SIGNATURES

@@ -55,6 +55,7 @@ typedef enum { ncclFloat64 = 8 } ncclDataType_t;
 #include "../../include/xgpr_hip_subst_var_scan.h"
 #include "../../include/xgpr_hip_indel_var_scan.h"
 #include "../../include/xgpr_hip_pair_scan.h"
+#include "../../include/xgpr_hip/pool_edits.h"
 
 namespace {
 
@@ -79,6 +80,7 @@ namespace {
 #include "pair_scan.inc"
 #include "var_scan.inc"
 #include "pool_input_grad.inc"
+#include "pool_edits.inc"
 #include "cluster.inc"
 
 }  // namespace
@@ -665,6 +667,25 @@ int xgpr_conv_token_pair_scan_f32(const uint8_t *tokens, const float *table, con
                                   void *workspace, size_t workspace_bytes, void *stream) {
     return pair_scan_impl(tokens, table, w, out, radem, chi, seqlen_host, seqlen_dev, n, L, vocab, C, num_freqs, radem_shape2,
                           conv_width, scaling_type, fit_intercept, workspace, workspace_bytes, stream);
+}
+
+// ---- include/xgpr_hip/pool_edits.h
+int xgpr_conv_token_maxpool_edits_ok(long width, long vocab, long C, long num_rffs) {
+    return conv_token_maxpool_edits_ok_impl(width, vocab, C, num_rffs);
+}
+int xgpr_conv_token_maxpool_tables_f32(const uint8_t *tokens, const float *table, float *pm, float *sm, const int8_t *radem,
+                                       const float *chi, const int32_t *seqlen_host, const int32_t *seqlen_dev, long n, long L,
+                                       long vocab, long C, long num_rffs, long radem_shape2, long nseq, int conv_width, void *workspace,
+                                       size_t workspace_bytes, void *stream) {
+    return pool_tables_impl(tokens, table, pm, sm, radem, chi, seqlen_host, seqlen_dev, n, L, vocab, C, num_rffs, radem_shape2, nseq,
+                            conv_width, workspace, workspace_bytes, stream);
+}
+int xgpr_conv_token_maxpool_edits_f32(const uint8_t *tokens, const float *table, const float *pm, const float *sm, float *out,
+                                      const int8_t *radem, const float *chi, const int32_t *seqlen_host, const int32_t *seqlen_dev,
+                                      long n, long L, long vocab, long C, long num_rffs, long radem_shape2, long nseq, int conv_width,
+                                      int mode, long slot_lo, long nslots, void *workspace, size_t workspace_bytes, void *stream) {
+    return pool_edits_impl(tokens, table, pm, sm, out, radem, chi, seqlen_host, seqlen_dev, n, L, vocab, C, num_rffs, radem_shape2,
+                           nseq, conv_width, mode, slot_lo, nslots, workspace, workspace_bytes, stream);
 }
 
 int xgpr_selftest_lane_xor(int32_t *out, void *stream) {

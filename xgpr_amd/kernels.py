@@ -1456,6 +1456,171 @@ class Conv1dTwoLayerKernel(KernelBase):
         g = self.second_layer().input_gradient(pooled, weights, w_cols)
         return self.first_layer_gradient(input_x, sequence_length, g)
 
+    # ---- the exact effect of every single substitution, deletion and insertion: a maximum is order-free, so the
+    # pooled row of a mutant is max(prefix maxima left of the edit, suffix maxima right of it, the ~conv_width windows it creates)
+    EDITS = ("substitutions", "deletions", "insertions")
+    POOL_EDITS_ELEMS = 1 << 26       # float32 elements of mutant pooled rows one slab holds (either route)
+    EDIT_ROWS_ELEMS = 1 << 24        # float64 elements of second-layer features held at a time when a slab is reduced
+
+    def _edit_inputs(self, batch, sequence_length, edit):
+        if edit not in self.EDITS:
+            raise RuntimeError("edit must be one of 'substitutions', 'deletions', 'insertions'.")
+        if not isinstance(batch, TokenBatch):
+            raise RuntimeError("pool_edits needs sequences given as tokens (a TokenBatch).")
+        xs = batch.to(self.device)
+        lengths = self._lengths(xs, sequence_length)
+        n, L = xs.shape[0], xs.shape[1]
+        if lengths.shape[0] != n:
+            raise RuntimeError("sequence_length must hold one length per sequence.")
+        if n and (int(lengths.min()) < self.conv_width or int(lengths.max()) > L):
+            raise RuntimeError("All sequence lengths must be >= conv width and < array size.")
+        return xs, lengths
+
+    def _edit_geometry(self, xs, edit):
+        """-> (slots per sequence, rows per slot, slots per slab): slabs are cut on slot boundaries."""
+        L, V = xs.shape[1], xs.table.shape[0]
+        slots, per = (L + 1 if edit == "insertions" else L), (1 if edit == "deletions" else V)
+        return slots, per, int(min(max(1, self.POOL_EDITS_ELEMS // (per * self.init_rffs)), (1 << 24) - 1))
+
+    def _pool_edits_operator_ok(self, xs):
+        return bool(torch.device(self.device).type == "cuda" and xs.is_cuda and xs.tokens.is_contiguous()
+                    and ext.conv_token_maxpool_edits_ok(self.conv_width * xs.shape[2], xs.table.shape[0], xs.shape[2],
+                                                        self.init_rffs) == 1)
+
+    def pool_edits(self, batch, sequence_length, edit):
+        """Generator of (slot_lo, rows): the pooled first-layer rows (float32, what ``pool`` gives for the written-out mutant: equal
+        everywhere, bit for bit wherever not zero) of EVERY single-token mutant of the TokenBatch ``batch``, slab by slab.  ``edit``
+        "substitutions": slot = (sequence, position l), rows [nslots, V, init_rffs] -- token l replaced by table row v;
+        "deletions": slot = (sequence, position p), rows [nslots, init_rffs] -- NaN for a sequence of exactly conv_width tokens;
+        "insertions": slot = (sequence, gap g of L + 1), rows [nslots, V, init_rffs] -- row v inserted before g, g = the length
+        appends.  Slots are numbered sequence-major, a slab holds at most ``POOL_EDITS_ELEMS`` elements, and slots past a sequence's
+        length are exact zero rows.  The prefix / suffix maxima of the sequences' own windows are built once per call
+        (``ext.hipConvTokenMaxpoolTables``) and a mutant costs its about conv_width new windows (``ext.hipConvTokenMaxpoolEdits``)
+        instead of all of its windows; no mutant is written.  Where ``ext.conv_token_maxpool_edits_ok`` is 0, the tokens are not
+        contiguous or there is no HIP device the slabs come from ``pool_edits_composed``."""
+        xs, lengths = self._edit_inputs(batch, sequence_length, edit)
+        if not self._pool_edits_operator_ok(xs):
+            yield from self._pool_edits_composed(xs, lengths, edit)
+            return
+        n, L = xs.shape[0], xs.shape[1]
+        slots, per, step = self._edit_geometry(xs, edit)
+        F, table = self.init_rffs, xs.table.contiguous()
+        pm = torch.empty((n, L - self.conv_width + 2, F), dtype=torch.float32, device=self.device)
+        sm = torch.empty_like(pm)
+        if n:
+            ext.hipConvTokenMaxpoolTables(xs.tokens, table, pm, sm, self.radem_diag1, self.chi_arr1, lengths, self.conv_width)
+        for lo in range(0, n * slots, step):
+            cnt = min(step, n * slots - lo)
+            rows = torch.empty((cnt, F) if edit == "deletions" else (cnt, per, F), dtype=torch.float32, device=self.device)
+            ext.hipConvTokenMaxpoolEdits(xs.tokens, table, pm, sm, rows, self.radem_diag1, self.chi_arr1, lengths, self.conv_width,
+                                         edit, lo, cnt)
+            yield lo, rows
+
+    def pool_edits_composed(self, batch, sequence_length, edit):
+        """The same slabs from existing operators, at every window width and table size: a slab's mutants are written out as
+        token rows (L + 1 positions for the indels) and pooled with ``_pool_into``; then the contract's zero rows (no such position
+        or gap) and NaN rows (a deletion that leaves no window) are set.  Same slab boundaries as ``pool_edits``."""
+        xs, lengths = self._edit_inputs(batch, sequence_length, edit)
+        yield from self._pool_edits_composed(xs, lengths, edit)
+
+    def _pool_edits_composed(self, xs, lengths, edit):
+        n, L = xs.shape[0], xs.shape[1]
+        cw, F, dev = self.conv_width, self.init_rffs, self.device
+        slots, per, step = self._edit_geometry(xs, edit)
+        tokens, lens_dev = xs.tokens.contiguous(), torch.from_numpy(lengths).to(dev).long()
+        k = torch.arange(L + 1, device=dev)[None, :]
+        for lo in range(0, n * slots, step):
+            cnt = min(step, n * slots - lo)
+            ids = torch.arange(lo * per, (lo + cnt) * per, device=dev)
+            seq, site, tok = ids // (slots * per), (ids // per) % slots, ids % per
+            slen = lens_dev[seq]
+            if edit == "substitutions":
+                mut = tokens[seq]
+                mut[torch.arange(ids.shape[0], device=dev), site] = tok.to(torch.uint8)      # (past the length: never read)
+                mlen, gone, nan = slen, site >= slen, None
+            elif edit == "deletions":
+                pos = torch.where(slen > cw, site, L + 1)                                 # (no mutant: the sequence itself, overwritten below)
+                mut = torch.gather(tokens[seq], 1, (k + (k >= pos[:, None]).long()).clamp_(max=L - 1))
+                mlen, gone = (slen - 1).clamp_(min=cw), site >= slen
+                nan = (slen == cw) & ~gone
+            else:
+                mut = torch.gather(tokens[seq], 1, (k - (k > site[:, None]).long()).clamp_(max=L - 1))
+                mut[torch.arange(ids.shape[0], device=dev), site] = tok.to(torch.uint8)
+                mlen, gone, nan = slen + (site <= slen).long(), site > slen, None
+            rows = torch.zeros((ids.shape[0], F), dtype=torch.float32, device=dev)
+            self._pool_into(TokenBatch(mut.contiguous(), xs.table), mlen.to(torch.int32).cpu().numpy(), rows)
+            if nan is not None:
+                rows.masked_fill_(nan[:, None], float("nan"))
+            rows.masked_fill_(gone[:, None], 0.0)
+            yield lo, rows if edit == "deletions" else rows.view(cnt, per, F)
+
+    def _edit_rows_results(self, rows, w, var):
+        """Pooled rows [m, init_rffs] float32 -> (features . w [m], z_v^T var z_v [m] or None) in float64, through the second layer's
+        own operators (``second_layer().transform_x``: sigma and the RBF features) at most ``EDIT_ROWS_ELEMS`` feature elements at a
+        time.  The ONE place where a slab of either row source becomes results."""
+        m = rows.shape[0]
+        second = self.second_layer()
+        mean = torch.empty(m, dtype=torch.float64, device=self.device)
+        quad = None if var is None else torch.empty(m, dtype=torch.float64, device=self.device)
+        step = max(1, self.EDIT_ROWS_ELEMS // self.num_rffs)
+        for lo in range(0, m, step):
+            z = second.transform_x(rows[lo:lo + step])
+            mean[lo:lo + step] = (z * w[None, :]).sum(dim=1)
+            if var is not None:
+                zv = z[:, :var.shape[0]]
+                quad[lo:lo + step] = (zv * (var @ zv.T).T).sum(dim=1)
+        return mean, quad
+
+    def edit_scan(self, batch, sequence_length, weights, edit, var=None, composed=False):
+        """float64 device tensor -- [n, L, V] for ``edit`` "substitutions", [n, L] for "deletions", [n, L + 1, V] for "insertions" --:
+        ``transform_x(mutant) @ weights`` minus ``transform_x(sequence) @ weights`` for every single-token mutant of the
+        TokenBatch, exact (the mutants' pooled rows are those of ``pool``; see ``pool_edits``).  Exactly 0 at a substitution's own
+        token and for positions / gaps past the length; NaN for the deletions of a sequence of exactly conv_width tokens.  With
+        ``var`` (nvar x nvar, float64) the return is (scan, quad): quad holds z'^T var z' of the mutant's first nvar second-layer
+        features, the quadratic form of ``predict(get_var=True)`` (0 past the length, NaN where scan is).  ``composed`` takes the
+        rows from ``pool_edits_composed``; both sources go through ``_edit_rows_results`` with the same slab boundaries."""
+        xs, lengths = self._edit_inputs(batch, sequence_length, edit)
+        w = weights if isinstance(weights, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(weights))
+        w = w.to(self.device, torch.float64).contiguous()
+        if w.dim() != 1 or w.shape[0] != self.num_rffs:
+            raise RuntimeError("weights must be one vector of num_rffs values.")
+        vm = None
+        if var is not None:
+            vm = (var if isinstance(var, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(var))).to(self.device, torch.float64)
+            if vm.dim() != 2 or vm.shape[0] != vm.shape[1] or not 1 <= vm.shape[0] <= self.num_rffs:
+                raise RuntimeError("var must be a square matrix over the first nvar <= num_rffs features.")
+        n, L, V, dev = xs.shape[0], xs.shape[1], xs.table.shape[0], self.device
+        slots, per, _ = self._edit_geometry(xs, edit)
+        base = torch.zeros(0, dtype=torch.float64, device=dev)
+        if n:
+            base = self._edit_rows_results(self._first_layer(xs, lengths), w, None)[0]
+        scan = torch.empty(n * slots * per, dtype=torch.float64, device=dev)
+        quad = None if vm is None else torch.empty_like(scan)
+        source = self._pool_edits_composed if composed or not self._pool_edits_operator_ok(xs) else self.pool_edits
+        for lo, rows in source(xs, lengths, edit):
+            rows = rows.reshape(-1, self.init_rffs)
+            if edit == "deletions":
+                rows = torch.nan_to_num(rows, nan=0.0)                                    # (set to NaN by definition below)
+            mean, qd = self._edit_rows_results(rows, w, vm)
+            ids = torch.arange(lo * per, lo * per + rows.shape[0], device=dev)
+            scan[ids] = mean - base[ids // (slots * per)]
+            if quad is not None:
+                quad[ids] = qd
+        shape = (n, slots) if edit == "deletions" else (n, slots, V)
+        scan = scan.view(shape)
+        lens_dev = torch.from_numpy(lengths).to(dev).long()
+        site = torch.arange(slots, device=dev)[None, :]
+        gone = site > lens_dev[:, None] if edit == "insertions" else site >= lens_dev[:, None]
+        nan = (lens_dev[:, None] == self.conv_width) & ~gone if edit == "deletions" else None
+        outs = [scan] if quad is None else [scan, quad.view(shape)]
+        for t in outs:
+            if nan is not None:
+                t.masked_fill_(nan, float("nan"))
+            t.masked_fill_(gone if edit == "deletions" else gone[:, :, None], 0.0)
+        if edit == "substitutions":                      # the own token: the mutant is the sequence itself
+            scan.masked_fill_(torch.arange(V, device=dev)[None, None, :] == xs.tokens.long()[:, :, None], 0.0)
+        return scan if quad is None else (scan, outs[1])
+
     # the resident float32 cache holds complete feature rows, as for the other sequence kernels
     def cache_ok(self):
         return self.num_freqs <= 16384

@@ -237,7 +237,8 @@ class xGPRegression(_ModelBase):
         sequence's length and the sequence's own variance at its own token.  It has a per-window decomposition too: the
         substitution moves the variance columns z by a vector built from the conv_width covering windows alone, so the quadratic
         form needs those windows' first tile and one nvar x nvar contraction per mutant, not the mutants' feature rows
-        (``ConvSORFKernel.substitution_variance_scan``)."""
+        (``ConvSORFKernel.substitution_variance_scan``).  ``predict_single_edits`` returns the same array for these
+        kernels and serves Conv1dTwoLayer too."""
         if self.weights is None:
             raise RuntimeError("Model has not yet been successfully fitted.")
         if get_var and self.var is None:
@@ -271,11 +272,16 @@ class xGPRegression(_ModelBase):
         var[np.arange(input_x.shape[1])[None, :] >= sequence_lengths[:, None]] = 0
         return scan, var * self.trainy_std ** 2
 
-    def _token_scan_input(self, name, input_x, sequence_lengths, token_table):
-        """The refusals ``predict_substitutions`` makes, for the other position-by-position scans -> (TokenBatch, lengths)."""
+    def _token_scan_input(self, name, input_x, sequence_lengths, token_table, two_layer=False):
+        """The refusals ``predict_substitutions`` makes, for the other position-by-position scans -> (TokenBatch, lengths).
+        ``two_layer``: the scan serves Conv1dTwoLayer as well."""
         if self.weights is None:
             raise RuntimeError("Model has not yet been successfully fitted.")
-        if type(self.kernel) is not ConvSORFKernel:
+        if two_layer and type(self.kernel) not in (ConvSORFKernel, Conv1dTwoLayerKernel):
+            raise RuntimeError(f"{name} is available for the sequence and graph kernels Conv1dRBF, Conv1dMatern, Conv1dCauchy, "
+                               "GraphRBF, GraphMatern and GraphCauchy and for Conv1dTwoLayer on token input; the fixed-vector "
+                               f"kernels, Linear and MiniARD are not supported (this model's kernel is '{self.kernel_choice}').")
+        if not two_layer and type(self.kernel) is not ConvSORFKernel:
             raise RuntimeError(f"{name} is available for the sequence and graph kernels Conv1dRBF, Conv1dMatern, "
                                "Conv1dCauchy, GraphRBF, GraphMatern and GraphCauchy on token input; Conv1dTwoLayer, the "
                                "fixed-vector kernels, Linear and MiniARD are not supported "
@@ -304,7 +310,7 @@ class xGPRegression(_ModelBase):
         kernels and refusals as for ``predict_substitutions``.  One HIP kernel transforms the shared windows alone and writes no
         mutant (``ConvSORFKernel.pair_substitution_scan``).  The output is large -- 14.5 MB per sequence of a
         512-position array at conv_width 9 and V = 21 --, which is why ``chunk_size``, the sequences that go to the device at a
-        time, is small."""
+        time, is small.  (The single edits of every sequence kernel, Conv1dTwoLayer included: ``predict_single_edits``.)"""
         input_x, sequence_lengths = self._token_scan_input("predict_substitution_pairs", input_x, sequence_lengths, token_table)
         n, L, V = input_x.shape[0], input_x.shape[1], input_x.table.shape[0]
         out = np.zeros((n, L, self.kernel.conv_width - 1, V, V))
@@ -327,7 +333,8 @@ class xGPRegression(_ModelBase):
         max(0, lambda^2 + lambda^2 z'^T var z') --, exactly 0 for p >= the length and g > the length and NaN where the deletions
         are NaN.  The identity of ``predict_substitutions(get_var=True)`` holds with the mutant's normaliser r': the sequence's own
         variance columns are rescaled by r' / r and moved by r' times a vector built from the windows at the edit site alone
-        (``ConvSORFKernel.indel_variance_scan``)."""
+        (``ConvSORFKernel.indel_variance_scan``).  ``predict_single_edits`` returns the same arrays for these kernels
+        and serves Conv1dTwoLayer too."""
         if get_var and self.weights is not None and self.var is None:
             raise RuntimeError("Variance was requested but suppress_var was selected when fitting.")
         input_x, sequence_lengths = self._token_scan_input("predict_indels", input_x, sequence_lengths, token_table)
@@ -351,6 +358,52 @@ class xGPRegression(_ModelBase):
             var[np.arange(first)[None, :] >= sequence_lengths[:, None] + half] = 0
             out.append(var * self.trainy_std ** 2)
         return means + tuple(out)
+
+    def predict_single_edits(self, input_x, sequence_lengths=None, token_table=None, get_var=False, chunk_size=16):
+        """The exact effect of EVERY single-token edit on ``predict``, for every sequence kernel (no counterpart in the reference)
+        -> dict of numpy float64 arrays in the units of y: "substitutions" [N, L, V], "deletions" [N, L] and "insertions"
+        [N, L + 1, V], each the predicted mean of the mutant minus that of the sequence itself, as ``predict_substitutions`` and
+        ``predict_indels`` define them -- exactly 0 at a sequence's own token and past its length, NaN for the deletions of a
+        sequence of exactly conv_width tokens.  With ``get_var`` also "substitutions_var", "deletions_var" and "insertions_var": the
+        predictive variance of every mutant as ``predict(get_var=True)`` gives it, trainy_std^2 max(0, lambda^2 + lambda^2 z'^T var z'),
+        0 past the length and NaN where the deletions are.  For the sequence and graph kernels Conv1d* / Graph* the arrays ARE those
+        of ``predict_substitutions`` and ``predict_indels``.  For Conv1dTwoLayer the mutants' pooled first-layer rows come from the
+        prefix and suffix maxima of the sequence's own windows and the about conv_width windows an edit creates -- a maximum is
+        order-free, so this is exact and no mutant is written -- and go through the second layer slab by slab (DESIGN.md 3.25;
+        ``Conv1dTwoLayerKernel.edit_scan``).  Input as for ``predict_substitutions``: a TokenBatch, or integer tokens [N, L] with
+        ``token_table``; ``sequence_lengths`` is required.  ``chunk_size`` sequences go to the device at a time."""
+        if get_var and self.weights is not None and self.var is None:
+            raise RuntimeError("Variance was requested but suppress_var was selected when fitting.")
+        names = ("substitutions", "deletions", "insertions")
+        if type(self.kernel) is not Conv1dTwoLayerKernel:
+            input_x, sequence_lengths = self._token_scan_input("predict_single_edits", input_x, sequence_lengths, token_table,
+                                                               two_layer=True)
+            sub = self.predict_substitutions(input_x, sequence_lengths, chunk_size=chunk_size, get_var=get_var)
+            ind = self.predict_indels(input_x, sequence_lengths, chunk_size=chunk_size, get_var=get_var)
+            if not get_var:
+                return dict(zip(names, (sub,) + tuple(ind)))
+            return dict(zip(names + tuple(nm + "_var" for nm in names), (sub[0], ind[0], ind[1], sub[1], ind[2], ind[3])))
+        input_x, sequence_lengths = self._token_scan_input("predict_single_edits", input_x, sequence_lengths, token_table, two_layer=True)
+        n, L, V = input_x.shape[0], input_x.shape[1], input_x.table.shape[0]
+        lambda_ = float(self.kernel.get_lambda())
+        out = {}
+        for name, shape in zip(names, ((n, L, V), (n, L), (n, L + 1, V))):
+            mean = np.zeros(shape)
+            var = np.zeros(shape) if get_var else None
+            for i in range(0, n, chunk_size):
+                res = self.kernel.edit_scan(input_x[i:i + chunk_size], sequence_lengths[i:i + chunk_size], self.weights, name,
+                                            var=self.var if get_var else None)
+                mean[i:i + chunk_size] = (res[0] if get_var else res).cpu().numpy()
+                if get_var:
+                    var[i:i + chunk_size] = res[1].cpu().numpy()
+            out[name] = mean * self.trainy_std
+            if get_var:
+                var = lambda_ ** 2 + lambda_ ** 2 * var
+                var[var < 0] = 0                                 # (a NaN stays a NaN)
+                first = np.arange(shape[1])[None, :]
+                var[first > sequence_lengths[:, None] if name == "insertions" else first >= sequence_lengths[:, None]] = 0
+                out[name + "_var"] = var * self.trainy_std ** 2
+        return out
 
     def predict_window_scores(self, input_x, sequence_lengths=None, token_table=None, chunk_size=64):
         """The share of every k-mer window in ``predict`` (no counterpart in the reference) -> numpy float64 [N, L]: entry

@@ -1328,6 +1328,69 @@ def hipConvTokenMaxpoolInputGrad(tokens, table, g, out, argmax, radem, chi, seql
         table.shape[0], table.shape[1], stride, chi.shape[0], radem.shape[2], int(conv_width), wp, wn, _stream()))
 
 
+POOL_EDIT_MODES = {"deletions": 1, "insertions": 2, "substitutions": 3}      # include/xgpr_hip/pool_edits.h XGPR_POOL_EDIT_*
+
+
+def conv_token_maxpool_edits_ok(width, vocab, C, num_rffs):
+    """Whether hipConvTokenMaxpoolTables / hipConvTokenMaxpoolEdits serve a window of ``width`` = conv_width * C elements over a
+    table of ``vocab`` rows and ``C`` columns with ``num_rffs`` filters (the shapes of ``conv_token_maxpool_input_grad_ok``)."""
+    return int(_LIB.xgpr_conv_token_maxpool_edits_ok(int(width), int(vocab), int(C), int(num_rffs)))
+
+
+def _pool_edit_operands(tokens, table, pm, sm, radem, chi, seqlen, conv_width, workspace):
+    t = _dev(tokens, "tokens", torch.uint8, 2)
+    tab = _dev(table, "table", torch.float32, 2)
+    p = _dev(pm, "pm", torch.float32, 3)
+    s = _dev(sm, "sm", torch.float32, 3)
+    r = _radem3(radem)
+    c = _dev(chi, "chi", torch.float32, 1)
+    n, L = tokens.shape
+    host, dev = _seqlens(seqlen, tokens.device)
+    rows = (n, L - int(conv_width) + 2, chi.shape[0])
+    if tuple(pm.shape) != rows or tuple(sm.shape) != rows:
+        raise RuntimeError("Wrong array sizes.")
+    if workspace is None:
+        ws, wp, wn = _workspace(_LIB.xgpr_rbf_workspace_bytes(radem.shape[2]), tokens.device)
+    else:
+        ws, wp, wn = workspace, C.c_void_p(workspace.data_ptr()), C.c_size_t(workspace.numel() * workspace.element_size())
+    return (t, tab, p, s, r, c, C.c_void_p(host.ctypes.data), C.c_void_p(dev.data_ptr())), host, ws, wp, wn
+
+
+def hipConvTokenMaxpoolTables(tokens, table, pm, sm, radem, chi, seqlen, conv_width, workspace=None):
+    """``pm``, ``sm`` [n, L - conv_width + 2, F] float32 (both OVERWRITTEN as a whole) <- the prefix and suffix maxima of the
+    max-pool operator's projections over the k-mer windows of ``table[tokens]`` (include/xgpr_hip/pool_edits.h): ``pm[i, j]`` is what
+    hipConvTokenMaxpool leaves in a zeroed row for the first j windows of sequence i, ``sm[i, j]`` for the windows from j on; rows
+    past a sequence's window count are exact zeros.  ``tokens`` [n, L] uint8, ``table`` [V, C] float32 UNSCALED, ``seqlen`` int32
+    on the host.  Shapes for which ``conv_token_maxpool_edits_ok`` is 0 raise RuntimeError and launch nothing."""
+    ops, host, ws, wp, wn = _pool_edit_operands(tokens, table, pm, sm, radem, chi, seqlen, conv_width, workspace)
+    t, tab, p, s, r, c, hp, dp = ops
+    return _lib.check(_LIB.xgpr_conv_token_maxpool_tables_f32(
+        t, tab, p, s, r, c, hp, dp, tokens.shape[0], tokens.shape[1], table.shape[0], table.shape[1], chi.shape[0], radem.shape[2],
+        host.shape[0], int(conv_width), wp, wn, _stream()))
+
+
+def hipConvTokenMaxpoolEdits(tokens, table, pm, sm, out, radem, chi, seqlen, conv_width, mode, slot_lo, nslots, workspace=None):
+    """``out`` (float32, OVERWRITTEN) <- the pooled first-layer row of every single-token mutant in the slots
+    [slot_lo, slot_lo + nslots) of the flattened (sequence, slot) index, from the tables of hipConvTokenMaxpoolTables and about
+    conv_width new windows per mutant; no mutant is written.  ``mode`` "substitutions": slot = position l of L, ``out``
+    [nslots, V, F]; "deletions": slot = position p of L, ``out`` [nslots, F] (NaN rows for a sequence of exactly conv_width
+    tokens); "insertions": slot = gap g of L + 1 (g = the length appends), ``out`` [nslots, V, F].  Slots past a sequence are
+    exact zero rows.  Every value equals what hipConvTokenMaxpool leaves in a zeroed row for the written-out mutant, bit for bit
+    wherever it is not zero; the sign of a zero is unspecified."""
+    if mode not in POOL_EDIT_MODES:
+        raise RuntimeError("mode must be one of 'substitutions', 'deletions', 'insertions'.")
+    ops, host, ws, wp, wn = _pool_edit_operands(tokens, table, pm, sm, radem, chi, seqlen, conv_width, workspace)
+    t, tab, p, s, r, c, hp, dp = ops
+    F, V = chi.shape[0], table.shape[0]
+    shape = (int(nslots), F) if mode == "deletions" else (int(nslots), V, F)
+    if isinstance(out, torch.Tensor) and tuple(out.shape) != shape:
+        raise RuntimeError("Wrong array sizes.")
+    o = _dev(out, "out", torch.float32, len(shape))
+    return _lib.check(_LIB.xgpr_conv_token_maxpool_edits_f32(
+        t, tab, p, s, o, r, c, hp, dp, tokens.shape[0], tokens.shape[1], V, table.shape[1], F, radem.shape[2], host.shape[0],
+        int(conv_width), POOL_EDIT_MODES[mode], int(slot_lo), int(nslots), wp, wn, _stream()))
+
+
 def kmeans_ok(num_rffs, k):
     """Whether hipKMeansAssign / hipKMeansUpdate serve ``k`` centres over rows of ``num_rffs`` columns (a multiple of 4, at
     most 256 centres)."""
