@@ -163,6 +163,16 @@ POOL_EDITS_ABI = {
     "xgpr_conv_token_maxpool_edits_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _l, _l, _l, _l, _l, _l, _l, _i, _i, _l, _l, _vp,
                                           _sz, _vp],
 }
+# ... and include/xgpr_hip/edit_proj.h, the thirteenth (tests/test_edit_proj_host.py); named like the twelfth's table, for its reason; its
+# *_workspace_bytes function returns size_t
+EDIT_PROJ_ABI = {
+    "xgpr_conv_token_edit_proj_ok": [_l, _l, _l, _l, _l, _l],
+    "xgpr_conv_token_edit_proj_workspace_bytes": [_l, _l, _l],
+    "xgpr_conv_token_subst_proj_f32": [_vp, _vp, _vp, _l, _vp, _vp, _vp, _vp, _vp, _vp, _l, _l, _l, _l, _l, _l, _l, _l, _i, _i, _i, _l,
+                                       _vp, _sz, _vp],
+    "xgpr_conv_token_indel_proj_f32": [_vp, _vp, _vp, _l, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _l, _l, _l, _l, _l, _l, _l, _l, _i, _i,
+                                       _i, _l, _vp, _sz, _vp],
+}
 STRING_FUNCS = ["xgpr_last_error", "xgpr_build_arch", "xgpr_build_id"]
 
 _lib = None
@@ -185,10 +195,11 @@ def load():
                        + list(SEQ_INPUT_GRAD_SIGNATURES.items()) + list(POOL_INPUT_GRAD_SIGNATURES.items()) + list(CLUSTER_SIGNATURES.items())
                        + list(SUBST_SCAN_SIGNATURES.items()) + list(INDEL_SCAN_SIGNATURES.items())
                        + list(SUBST_VAR_SCAN_SIGNATURES.items()) + list(INDEL_VAR_SCAN_SIGNATURES.items())
-                       + list(PAIR_SCAN_SIGNATURES.items()) + list(POOL_EDITS_ABI.items())):
+                       + list(PAIR_SCAN_SIGNATURES.items()) + list(POOL_EDITS_ABI.items()) + list(EDIT_PROJ_ABI.items())):
         fn = getattr(lib, name)
         fn.argtypes = args
-        sized = name in CLUSTER_SIGNATURES or name in SUBST_VAR_SCAN_SIGNATURES or name in INDEL_VAR_SCAN_SIGNATURES
+        sized = (name in CLUSTER_SIGNATURES or name in SUBST_VAR_SCAN_SIGNATURES or name in INDEL_VAR_SCAN_SIGNATURES
+                 or name in EDIT_PROJ_ABI)
         fn.restype = C.c_size_t if sized and name.endswith("_workspace_bytes") else C.c_int
     for name, args in SIZE_FUNCS.items():
         fn = getattr(lib, name)

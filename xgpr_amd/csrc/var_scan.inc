@@ -485,7 +485,7 @@ constexpr VarScanOp INDEL_VAR_OP = {1, "the indel variance scan serves windows o
 // by halves); `outs_ok`: an output group too
 int var_scan_check(const VarScanOp &op, const int32_t *seqlen_host, long n, long L, long vocab, long C, long num_freqs, long R, long nvar,
                    long vm_stride, int conv_width, int scaling_type, long slab_rows, const void *workspace, size_t wbytes, bool bufs_ok,
-                   bool outs_ok, bool *launch) {
+                   bool outs_ok, bool *launch, long K = 1, long pm_stride = 1) {
     *launch = false;
     if (n < 0 || L < 1 || C < 1) return fail(XGPR_ERR_ARRAY_DIMS, "incorrect array dims passed");
     if (scaling_type < 0 || scaling_type > 2) return fail(XGPR_ERR_ARRAY_DIMS, "scaling_type must be 0, 1 or 2");
@@ -495,13 +495,15 @@ int var_scan_check(const VarScanOp &op, const int32_t *seqlen_host, long n, long
     if (nvar < 2 || (nvar & 1) != 0 || nvar > 2 * num_freqs)
         return fail(XGPR_ERR_ARRAY_DIMS, "nvar must be an even number, 2 .. 2 * num_freqs");
     if (vm_stride < nvar) return fail(XGPR_ERR_ARRAY_SIZES, "vm_stride is shorter than nvar");
+    if (K < 1) return fail(XGPR_ERR_ARRAY_DIMS, "K must be at least 1");                     // (the projections of edit_proj.inc alone)
+    if (pm_stride < K) return fail(XGPR_ERR_ARRAY_SIZES, "pm_stride is shorter than K");
     if (slab_rows < 0 || slab_rows % 16 != 0) return fail(XGPR_ERR_ARRAY_DIMS, "slab_rows must be 0 or a multiple of 16");
     if (n > 0) {
         int rc = check_seqlens(seqlen_host, n, n, L, conv_width);
         if (rc) return rc;
     }
     if (vocab < 1 || vocab > 256) return fail(XGPR_ERR_ARRAY_DIMS, "token table: vocab must be 1 .. 256 (uint8 tokens)");
-    if (!var_scan_ok(win, vocab, C, num_freqs, nvar)) return fail(XGPR_ERR_UNSUPPORTED, op.unsupported);
+    if (!var_scan_ok(win, vocab, C, num_freqs, nvar) || K > SV_MAX_NVAR) return fail(XGPR_ERR_UNSUPPORTED, op.unsupported);
     if (n == 0) return 0;
     if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 7) != 0 || wbytes < var_scan_workspace_bytes_impl(R, nvar, slab_rows))
         return fail(XGPR_ERR_WORKSPACE, op.workspace);
@@ -512,9 +514,11 @@ int var_scan_check(const VarScanOp &op, const int32_t *seqlen_host, long n, long
     return 0;
 }
 
-// the slabs of one row set: `rows` rows of `per_slot` rows per slot, into p.out under p.u, p.q
-template <int MODE>
-int var_scan_slabs(VarScanArgs p, long rows, long per_slot, long slab, int lg, hipStream_t st) {
+// the slabs of one row set: `rows` rows of `per_slot` rows per slot.  `second(p, MAP{}, blocks)` launches the slab's second kernel over
+// `blocks` workgroups of 64 rows under the row map of the row set: the quadratic form (quad_launcher: into p.out under p.u, p.q) or the
+// projection of edit_proj.inc
+template <int MODE, class SECOND>
+int var_scan_slabs(VarScanArgs p, long rows, long per_slot, long slab, int lg, hipStream_t st, SECOND second) {
     using MAP = std::conditional_t<MODE == EDIT_SUBST, SubstRowMap, std::conditional_t<MODE == EDIT_DEL, DelRowMap, InsRowMap>>;
     for (long lo = 0; lo < rows; lo += slab) {
         p.row_lo = lo;
@@ -531,11 +535,16 @@ int var_scan_slabs(VarScanArgs p, long rows, long per_slot, long slab, int lg, h
                               "var_delta_kernel launch", p);
         });
         if (rc) return rc;
-        rc = launch(var_quad_kernel<MAP>, dim3((unsigned)((p.row_hi - lo + 63) / 64)), dim3(256), 0, st,
-                    "var_quad_kernel launch", p);
+        rc = second(p, MAP{}, (unsigned)((p.row_hi - lo + 63) / 64));
         if (rc) return rc;
     }
     return 0;
+}
+
+inline auto quad_launcher(hipStream_t st) {
+    return [st](const VarScanArgs &p, auto map, unsigned blocks) {
+        return launch(var_quad_kernel<decltype(map)>, dim3(blocks), dim3(256), 0, st, "var_quad_kernel launch", p);
+    };
 }
 
 int subst_var_scan_impl(const uint8_t *tokens, const float *table, const double *vm, long vm_stride, const double *u, const double *q,
@@ -555,7 +564,8 @@ int subst_var_scan_impl(const uint8_t *tokens, const float *table, const double 
     rc = pack_masks(radem, (uint64_t *)workspace, R, p.s.ig.MW, st);
     if (rc) return rc;
     p.u = u; p.q = q; p.out = out;
-    return var_scan_slabs<EDIT_SUBST>(p, n * L * vocab, vocab, var_slab_rows(nvar, slab_rows), ilog2(padded_width((long)conv_width * C)), st);
+    return var_scan_slabs<EDIT_SUBST>(p, n * L * vocab, vocab, var_slab_rows(nvar, slab_rows), ilog2(padded_width((long)conv_width * C)), st,
+                                      quad_launcher(st));
 }
 
 int indel_var_scan_impl(const uint8_t *tokens, const float *table, const double *vm, long vm_stride, const double *u_del, const double *q_del,
@@ -581,12 +591,12 @@ int indel_var_scan_impl(const uint8_t *tokens, const float *table, const double 
     const int lg = ilog2(padded_width((long)conv_width * C));
     if (del) {
         p.u = u_del; p.q = q_del; p.out = out_del;
-        rc = var_scan_slabs<EDIT_DEL>(p, n * L, 1, slab, lg, st);
+        rc = var_scan_slabs<EDIT_DEL>(p, n * L, 1, slab, lg, st, quad_launcher(st));
         if (rc) return rc;
     }
     if (ins) {
         p.u = u_ins; p.q = q_ins; p.out = out_ins;
-        rc = var_scan_slabs<EDIT_INS>(p, n * (L + 1) * vocab, vocab, slab, lg, st);
+        rc = var_scan_slabs<EDIT_INS>(p, n * (L + 1) * vocab, vocab, slab, lg, st, quad_launcher(st));
     }
     return rc;
 }

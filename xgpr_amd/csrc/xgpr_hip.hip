@@ -56,6 +56,7 @@ typedef enum { ncclFloat64 = 8 } ncclDataType_t;
 #include "../../include/xgpr_hip_indel_var_scan.h"
 #include "../../include/xgpr_hip_pair_scan.h"
 #include "../../include/xgpr_hip/pool_edits.h"
+#include "../../include/xgpr_hip/edit_proj.h"
 
 namespace {
 
@@ -79,6 +80,7 @@ namespace {
 #include "edit_scan.inc"
 #include "pair_scan.inc"
 #include "var_scan.inc"
+#include "edit_proj.inc"
 #include "pool_input_grad.inc"
 #include "pool_edits.inc"
 #include "cluster.inc"
@@ -686,6 +688,31 @@ int xgpr_conv_token_maxpool_edits_f32(const uint8_t *tokens, const float *table,
                                       int mode, long slot_lo, long nslots, void *workspace, size_t workspace_bytes, void *stream) {
     return pool_edits_impl(tokens, table, pm, sm, out, radem, chi, seqlen_host, seqlen_dev, n, L, vocab, C, num_rffs, radem_shape2,
                            nseq, conv_width, mode, slot_lo, nslots, workspace, workspace_bytes, stream);
+}
+
+// ---- include/xgpr_hip/edit_proj.h
+int xgpr_conv_token_edit_proj_ok(long width, long vocab, long C, long num_freqs, long nvar, long K) {
+    return edit_proj_ok(width, vocab, C, num_freqs, nvar, K);
+}
+size_t xgpr_conv_token_edit_proj_workspace_bytes(long radem_shape2, long nvar, long slab_rows) {
+    return var_scan_workspace_bytes_impl(radem_shape2, nvar, slab_rows);
+}
+int xgpr_conv_token_subst_proj_f32(const uint8_t *tokens, const float *table, const double *pm, long pm_stride, const double *b, double *out,
+                                   const int8_t *radem, const float *chi, const int32_t *seqlen_host, const int32_t *seqlen_dev, long n,
+                                   long L, long vocab, long C, long num_freqs, long radem_shape2, long nvar, long K, int conv_width,
+                                   int scaling_type, int fit_intercept, long slab_rows, void *workspace, size_t workspace_bytes,
+                                   void *stream) {
+    return subst_proj_impl(tokens, table, pm, pm_stride, b, out, radem, chi, seqlen_host, seqlen_dev, n, L, vocab, C, num_freqs,
+                           radem_shape2, nvar, K, conv_width, scaling_type, fit_intercept, slab_rows, workspace, workspace_bytes, stream);
+}
+int xgpr_conv_token_indel_proj_f32(const uint8_t *tokens, const float *table, const double *pm, long pm_stride, const double *b_del,
+                                   const double *b_ins, double *out_del, double *out_ins, const int8_t *radem, const float *chi,
+                                   const int32_t *seqlen_host, const int32_t *seqlen_dev, long n, long L, long vocab, long C,
+                                   long num_freqs, long radem_shape2, long nvar, long K, int conv_width, int scaling_type,
+                                   int fit_intercept, long slab_rows, void *workspace, size_t workspace_bytes, void *stream) {
+    return indel_proj_impl(tokens, table, pm, pm_stride, b_del, b_ins, out_del, out_ins, radem, chi, seqlen_host, seqlen_dev, n, L, vocab,
+                           C, num_freqs, radem_shape2, nvar, K, conv_width, scaling_type, fit_intercept, slab_rows, workspace,
+                           workspace_bytes, stream);
 }
 
 int xgpr_selftest_lane_xor(int32_t *out, void *stream) {

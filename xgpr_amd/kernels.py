@@ -1002,6 +1002,166 @@ class ConvSORFKernel(KernelBase):
         ins.masked_fill_((k > lens_dev[:, None])[:, :, None], 0.0)
         return dele, ins
 
+    # ---- the projection of every single edit's columns on a caller's matrix: the joint posterior of the neighbourhood
+    def _proj_scan_inputs(self, batch, sequence_length, proj):
+        if not isinstance(batch, TokenBatch):
+            raise RuntimeError("the projection scans need sequences given as tokens (a TokenBatch).")
+        xs = self.scaled_f32(batch)
+        lengths = self._host_lengths(xs, sequence_length)
+        if lengths.shape[0] != xs.shape[0]:
+            raise RuntimeError("sequence_length must hold one length per sequence.")
+        pm = proj if isinstance(proj, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(proj))
+        pm = pm.to(self.device, torch.float64)
+        if pm.dim() != 2 or not 1 <= pm.shape[0] <= self.num_rffs or pm.shape[1] < 1:
+            raise RuntimeError("proj must be a matrix [nvar, K] over the first 1 .. num_rffs feature columns, K >= 1.")
+        return xs, lengths, pm
+
+    def _proj_scan_columns(self, xs, lengths, pm):
+        """What the two projection scans feed their operator from -> (``proj`` padded with a zero row to an even nvar, the sequences'
+        own first columns: float32 rows of ``fill_feature_rows``, widened), or None where ``ext.conv_token_edit_proj_ok`` is 0 or the
+        tokens are not contiguous: the composed route."""
+        n, L, C = xs.shape
+        nvar, K = pm.shape
+        npad = nvar + (nvar & 1)
+        if not (xs.is_cuda and xs.tokens.is_contiguous()
+                and ext.conv_token_edit_proj_ok(self.conv_width * C, xs.table.shape[0], C, self.num_freqs, npad, K) == 1):
+            return None
+        self._check_lengths(lengths, n, L)
+        pp = torch.zeros((npad, K), dtype=torch.float64, device=self.device)
+        pp[:nvar] = pm
+        rows = torch.empty((n, self.num_rffs), dtype=torch.float32, device=self.device)
+        self.fill_feature_rows(xs, lengths, rows)
+        return pp, rows[:, :npad].to(torch.float64)
+
+    def substitution_projection_scan(self, batch, sequence_length, proj):
+        """float64 device tensor [n, L, V, K]: ``z'^T proj`` for the first ``nvar = proj.shape[0]`` columns z' of
+        ``transform_x(sequence with token l replaced by v)``, for every position l and every row v of the TokenBatch's table.  With
+        ``proj`` a factor of ``var`` (factor factor^T = var) the rows are a factor of the JOINT posterior covariance of all the
+        mutants -- ``substitution_variance_scan`` is their squared norms --; with ``proj = factor @ E`` for standard normal E they
+        are joint draws; with ``proj = var @ z*`` covariances with chosen sequences.  Exactly 0 past a sequence's length; the
+        sequence's own projection at its own token.  The delta kernels of ``substitution_variance_scan`` and one matrix-core kernel
+        per slab of mutants (``ext.hipConvTokenSubstProj``); the sequences' own columns come from ``fill_feature_rows`` (float32
+        rows, widened); an odd nvar is padded with a zero row.  Where ``ext.conv_token_edit_proj_ok`` is 0 (windows of more than
+        1024 elements, a table the LDS image does not hold, nvar or K > 2048) or the tokens are not contiguous the result comes from
+        ``substitution_projection_scan_composed``."""
+        xs, lengths, pm = self._proj_scan_inputs(batch, sequence_length, proj)
+        columns = self._proj_scan_columns(xs, lengths, pm)
+        if columns is None:
+            return self._subst_proj_composed(xs, lengths, pm)
+        pp, z = columns
+        n, L, _ = xs.shape
+        out = torch.empty((n, L, xs.table.shape[0], pm.shape[1]), dtype=torch.float64, device=self.device)
+        ext.hipConvTokenSubstProj(xs.tokens, xs.table.contiguous(), pp, (z @ pp).contiguous(), out, self.radem_diag, self.chi_arr,
+                                  lengths, self.conv_width, self.scaling_type, self.fit_intercept)
+        return out
+
+    def indel_projection_scan(self, batch, sequence_length, proj):
+        """(deletions [n, L, K], insertions [n, L + 1, V, K]), float64 device tensors: ``z'^T proj`` for the first
+        ``nvar = proj.shape[0]`` columns z' of ``transform_x(mutant)``, for the sequence without its token at position p and for
+        the sequence with row v of the TokenBatch's table inserted before position g (g = length appends); see
+        ``substitution_projection_scan`` for what ``proj`` makes of it.  Exactly 0 for p >= length and g > length; the deletions of
+        a sequence of exactly conv_width tokens (no window left) are NaN.  The mutant's columns are b + r' delta as in
+        ``indel_variance_scan`` (rho from the host lengths in float64); the delta kernels of that scan and one matrix-core kernel
+        per slab (``ext.hipConvTokenIndelProj``).  Where ``ext.conv_token_edit_proj_ok`` is 0 or the tokens are not contiguous the
+        result comes from ``indel_projection_scan_composed``."""
+        xs, lengths, pm = self._proj_scan_inputs(batch, sequence_length, proj)
+        columns = self._proj_scan_columns(xs, lengths, pm)
+        if columns is None:
+            return self._indel_proj_composed(xs, lengths, pm)
+        pp, z = columns
+        n, L, _ = xs.shape
+        V, K = xs.table.shape[0], pm.shape[1]
+        nk = lengths.astype(np.float64) - self.conv_width + 1
+        base = []
+        for nkm in (np.maximum(nk - 1, 1), nk + 1):      # (nk - 1 == 0: no mutant, the outputs are NaN whatever rho is)
+            ratio = nk / nkm
+            rho = {0: np.ones_like(ratio), 1: np.sqrt(ratio), 2: ratio}[self.scaling_type]
+            b = z * torch.from_numpy(rho).to(self.device)[:, None]
+            if self.fit_intercept:
+                b[:, 0] = 1.0                            # rho 1 + (1 - rho): the constant column is not rescaled
+            base.append((b @ pp).contiguous())
+        dele = torch.empty((n, L, K), dtype=torch.float64, device=self.device)
+        ins = torch.empty((n, L + 1, V, K), dtype=torch.float64, device=self.device)
+        ext.hipConvTokenIndelProj(xs.tokens, xs.table.contiguous(), pp, base[0], base[1], dele, ins, self.radem_diag, self.chi_arr,
+                                  lengths, self.conv_width, self.scaling_type, self.fit_intercept)
+        return dele, ins
+
+    def substitution_projection_scan_composed(self, batch, sequence_length, proj):
+        """The same result from existing operators, at every window width, table size, nvar and K: a bounded slice of (sequence,
+        position, token) mutants is written out as token rows, ``fill_feature_rows`` makes their float32 feature rows, and their
+        first nvar columns are multiplied with ``proj`` in float64 with torch.  At most ``COMPOSED_SCAN_ELEMS`` float32 row
+        elements are held at a time."""
+        return self._subst_proj_composed(*self._proj_scan_inputs(batch, sequence_length, proj))
+
+    def indel_projection_scan_composed(self, batch, sequence_length, proj):
+        """The same result from existing operators: bounded slices of deletion and insertion mutants are written out as token
+        rows of L + 1 positions, ``fill_feature_rows`` makes their float32 feature rows, their first nvar columns are multiplied
+        with ``proj`` in float64 with torch, and the zeros and NaNs of the contract are applied.  At most ``COMPOSED_SCAN_ELEMS``
+        float32 row elements are held at a time."""
+        return self._indel_proj_composed(*self._proj_scan_inputs(batch, sequence_length, proj))
+
+    def _row_projector(self, table, pm):
+        """f(token rows, int32 host lengths) -> the first nvar columns of their feature rows times pm, float64 [m, K]."""
+        def project(tok, lens):
+            rows = torch.empty((tok.shape[0], self.num_rffs), dtype=torch.float32, device=self.device)
+            self.fill_feature_rows(TokenBatch(tok.contiguous(), table), lens, rows)
+            return rows[:, :pm.shape[0]].to(torch.float64) @ pm
+        return project
+
+    def _subst_proj_composed(self, xs, lengths, pm):
+        n, L, _ = xs.shape
+        V, dev, K = xs.table.shape[0], self.device, pm.shape[1]
+        self._check_lengths(lengths, n, L)
+        project = self._row_projector(xs.table, pm)
+        tokens, lens_dev = xs.tokens.contiguous(), torch.from_numpy(lengths).to(dev)
+        step = max(1, self.COMPOSED_SCAN_ELEMS // max(self.num_rffs, K))
+        out = torch.empty((n, L, V, K), dtype=torch.float64, device=dev)
+        flat = out.view(-1, K)
+        for lo in range(0, n * L * V, step):
+            ids = torch.arange(lo, min(lo + step, n * L * V), device=dev)
+            seq, pos, tok = ids // (L * V), (ids // V) % L, ids % V
+            mut = tokens[seq]
+            # (a position past the length: the token lands outside the sequence and is never read; zeroed below)
+            mut[torch.arange(ids.shape[0], device=dev), pos] = tok.to(torch.uint8)
+            flat[lo:lo + step] = project(mut, lengths[seq.cpu().numpy()])
+        past = torch.arange(L, device=dev)[None, :] >= lens_dev[:, None]
+        return out.masked_fill_(past[:, :, None, None], 0.0)
+
+    def _indel_proj_composed(self, xs, lengths, pm):
+        n, L, _ = xs.shape
+        V, cw, dev, K = xs.table.shape[0], self.conv_width, self.device, pm.shape[1]
+        self._check_lengths(lengths, n, L)
+        project = self._row_projector(xs.table, pm)
+        tokens, lens_dev = xs.tokens.contiguous(), torch.from_numpy(lengths).to(dev).long()
+        step = max(1, self.COMPOSED_SCAN_ELEMS // max(self.num_rffs, K))
+        k = torch.arange(L + 1, device=dev)[None, :]
+        dele = torch.empty((n, L, K), dtype=torch.float64, device=dev)
+        flat = dele.view(-1, K)
+        for lo in range(0, n * L, step):
+            ids = torch.arange(lo, min(lo + step, n * L), device=dev)
+            seq, pos = ids // L, ids % L
+            pos = torch.where(lens_dev[seq] > cw, pos, L + 1)                   # (no mutant: the sequence itself, overwritten below)
+            src = (k + (k >= pos[:, None]).long()).clamp_(max=L - 1)            # position k of the mutant reads k + (k >= p)
+            mut = torch.gather(tokens[seq], 1, src)
+            mlen = (lens_dev[seq] - 1).clamp_(min=cw)                           # (entries with no mutant are overwritten below)
+            flat[lo:lo + step] = project(mut, mlen.to(torch.int32).cpu().numpy())
+        ins = torch.empty((n, L + 1, V, K), dtype=torch.float64, device=dev)
+        flat = ins.view(-1, K)
+        for lo in range(0, n * (L + 1) * V, step):
+            ids = torch.arange(lo, min(lo + step, n * (L + 1) * V), device=dev)
+            seq, gap, tok = ids // ((L + 1) * V), (ids // V) % (L + 1), ids % V
+            src = (k - (k > gap[:, None]).long()).clamp_(max=L - 1)             # k < g reads k, k > g reads k - 1 ...
+            mut = torch.gather(tokens[seq], 1, src)
+            mut[torch.arange(ids.shape[0], device=dev), gap] = tok.to(torch.uint8)      # ... and k == g is the new token
+            mlen = lens_dev[seq] + (gap <= lens_dev[seq]).long()               # (no such gap: the sequence itself, overwritten below)
+            flat[lo:lo + step] = project(mut, mlen.to(torch.int32).cpu().numpy())
+        # the contract's zeros (no such position or gap) and NaNs (a deletion that leaves no window)
+        pos = torch.arange(L, device=dev)[None, :]
+        dele.masked_fill_(((lens_dev[:, None] == cw) & (pos < lens_dev[:, None]))[:, :, None], float("nan"))
+        dele.masked_fill_((pos >= lens_dev[:, None])[:, :, None], 0.0)
+        ins.masked_fill_((k > lens_dev[:, None])[:, :, None, None], 0.0)
+        return dele, ins
+
     def grad_rows_ok(self):
         """Whether ``fill_grad_rows`` can write this kernel's float32 feature AND gradient rows, and the exact NMLL
         gradient's accumulations can run on them (nmll.calc_gradient_terms): a HIP device -- the writer serves every
@@ -1554,14 +1714,15 @@ class Conv1dTwoLayerKernel(KernelBase):
             rows.masked_fill_(gone[:, None], 0.0)
             yield lo, rows if edit == "deletions" else rows.view(cnt, per, F)
 
-    def _edit_rows_results(self, rows, w, var):
-        """Pooled rows [m, init_rffs] float32 -> (features . w [m], z_v^T var z_v [m] or None) in float64, through the second layer's
-        own operators (``second_layer().transform_x``: sigma and the RBF features) at most ``EDIT_ROWS_ELEMS`` feature elements at a
-        time.  The ONE place where a slab of either row source becomes results."""
+    def _edit_rows_results(self, rows, w, var, proj=None):
+        """Pooled rows [m, init_rffs] float32 -> (features . w [m], z_v^T var z_v [m] or None, z_p^T proj [m, K] or None) in float64,
+        through the second layer's own operators (``second_layer().transform_x``: sigma and the RBF features) at most
+        ``EDIT_ROWS_ELEMS`` feature elements at a time.  The ONE place where a slab of either row source becomes results."""
         m = rows.shape[0]
         second = self.second_layer()
         mean = torch.empty(m, dtype=torch.float64, device=self.device)
         quad = None if var is None else torch.empty(m, dtype=torch.float64, device=self.device)
+        pr = None if proj is None else torch.empty((m, proj.shape[1]), dtype=torch.float64, device=self.device)
         step = max(1, self.EDIT_ROWS_ELEMS // self.num_rffs)
         for lo in range(0, m, step):
             z = second.transform_x(rows[lo:lo + step])
@@ -1569,16 +1730,21 @@ class Conv1dTwoLayerKernel(KernelBase):
             if var is not None:
                 zv = z[:, :var.shape[0]]
                 quad[lo:lo + step] = (zv * (var @ zv.T).T).sum(dim=1)
-        return mean, quad
+            if proj is not None:
+                pr[lo:lo + step] = z[:, :proj.shape[0]] @ proj       # (the rows are there: a host-side product, no kernel of its own)
+        return mean, quad, pr
 
-    def edit_scan(self, batch, sequence_length, weights, edit, var=None, composed=False):
+    def edit_scan(self, batch, sequence_length, weights, edit, var=None, composed=False, proj=None):
         """float64 device tensor -- [n, L, V] for ``edit`` "substitutions", [n, L] for "deletions", [n, L + 1, V] for "insertions" --:
         ``transform_x(mutant) @ weights`` minus ``transform_x(sequence) @ weights`` for every single-token mutant of the
         TokenBatch, exact (the mutants' pooled rows are those of ``pool``; see ``pool_edits``).  Exactly 0 at a substitution's own
         token and for positions / gaps past the length; NaN for the deletions of a sequence of exactly conv_width tokens.  With
         ``var`` (nvar x nvar, float64) the return is (scan, quad): quad holds z'^T var z' of the mutant's first nvar second-layer
-        features, the quadratic form of ``predict(get_var=True)`` (0 past the length, NaN where scan is).  ``composed`` takes the
-        rows from ``pool_edits_composed``; both sources go through ``_edit_rows_results`` with the same slab boundaries."""
+        features, the quadratic form of ``predict(get_var=True)`` (0 past the length, NaN where scan is).  With ``proj`` ([nvar, K],
+        float64) a further tensor closes the return: z'^T proj of the mutant's first nvar second-layer features, [..., K] (0 past
+        the length, NaN where scan is; the sequence's own projection at its own token) -- see
+        ``ConvSORFKernel.substitution_projection_scan``.  ``composed`` takes the rows from ``pool_edits_composed``; both sources go
+        through ``_edit_rows_results`` with the same slab boundaries."""
         xs, lengths = self._edit_inputs(batch, sequence_length, edit)
         w = weights if isinstance(weights, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(weights))
         w = w.to(self.device, torch.float64).contiguous()
@@ -1589,6 +1755,11 @@ class Conv1dTwoLayerKernel(KernelBase):
             vm = (var if isinstance(var, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(var))).to(self.device, torch.float64)
             if vm.dim() != 2 or vm.shape[0] != vm.shape[1] or not 1 <= vm.shape[0] <= self.num_rffs:
                 raise RuntimeError("var must be a square matrix over the first nvar <= num_rffs features.")
+        pm = None
+        if proj is not None:
+            pm = (proj if isinstance(proj, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(proj))).to(self.device, torch.float64)
+            if pm.dim() != 2 or not 1 <= pm.shape[0] <= self.num_rffs or pm.shape[1] < 1:
+                raise RuntimeError("proj must be a matrix [nvar, K] over the first nvar <= num_rffs features, K >= 1.")
         n, L, V, dev = xs.shape[0], xs.shape[1], xs.table.shape[0], self.device
         slots, per, _ = self._edit_geometry(xs, edit)
         base = torch.zeros(0, dtype=torch.float64, device=dev)
@@ -1596,16 +1767,19 @@ class Conv1dTwoLayerKernel(KernelBase):
             base = self._edit_rows_results(self._first_layer(xs, lengths), w, None)[0]
         scan = torch.empty(n * slots * per, dtype=torch.float64, device=dev)
         quad = None if vm is None else torch.empty_like(scan)
+        prj = None if pm is None else torch.empty((scan.shape[0], pm.shape[1]), dtype=torch.float64, device=dev)
         source = self._pool_edits_composed if composed or not self._pool_edits_operator_ok(xs) else self.pool_edits
         for lo, rows in source(xs, lengths, edit):
             rows = rows.reshape(-1, self.init_rffs)
             if edit == "deletions":
                 rows = torch.nan_to_num(rows, nan=0.0)                                    # (set to NaN by definition below)
-            mean, qd = self._edit_rows_results(rows, w, vm)
+            mean, qd, pr = self._edit_rows_results(rows, w, vm, pm)
             ids = torch.arange(lo * per, lo * per + rows.shape[0], device=dev)
             scan[ids] = mean - base[ids // (slots * per)]
             if quad is not None:
                 quad[ids] = qd
+            if prj is not None:
+                prj[ids] = pr
         shape = (n, slots) if edit == "deletions" else (n, slots, V)
         scan = scan.view(shape)
         lens_dev = torch.from_numpy(lengths).to(dev).long()
@@ -1619,7 +1793,13 @@ class Conv1dTwoLayerKernel(KernelBase):
             t.masked_fill_(gone if edit == "deletions" else gone[:, :, None], 0.0)
         if edit == "substitutions":                      # the own token: the mutant is the sequence itself
             scan.masked_fill_(torch.arange(V, device=dev)[None, None, :] == xs.tokens.long()[:, :, None], 0.0)
-        return scan if quad is None else (scan, outs[1])
+        if prj is None:
+            return scan if quad is None else (scan, outs[1])
+        prj = prj.view(shape + (pm.shape[1],))
+        if nan is not None:
+            prj.masked_fill_(nan[:, :, None], float("nan"))
+        prj.masked_fill_(gone[:, :, None] if edit == "deletions" else gone[:, :, None, None], 0.0)
+        return (scan, prj) if quad is None else (scan, outs[1], prj)
 
     # the resident float32 cache holds complete feature rows, as for the other sequence kernels
     def cache_ok(self):

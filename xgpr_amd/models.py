@@ -405,6 +405,106 @@ class xGPRegression(_ModelBase):
                 out[name + "_var"] = var * self.trainy_std ** 2
         return out
 
+    # ---- the joint posterior over the single-edit neighbourhood: draws and batch picks (acquisition.py)
+    def _factor_of_var(self):
+        """F [nvar, nvar] with F F^T = 1/2 (var + var^T), negative eigenvalues clipped to 0 (``torch.linalg.eigh``); computed once
+        per ``self.var`` and kept next to it."""
+        cached = getattr(self, "_var_factor", None)
+        if cached is None or cached[0] is not self.var:
+            vals, vecs = torch.linalg.eigh(0.5 * (self.var + self.var.T))
+            cached = self._var_factor = (self.var, (vecs * torch.sqrt(vals.clamp(min=0.0))[None, :]).contiguous())
+        return cached[1]
+
+    def _joint_scan_input(self, name, input_x, sequence_lengths, token_table):
+        if self.weights is not None and self.var is None:
+            raise RuntimeError("Variance was requested but suppress_var was selected when fitting.")
+        return self._token_scan_input(name, input_x, sequence_lengths, token_table, two_layer=True)
+
+    def _edit_projections(self, input_x, sequence_lengths, proj):
+        """(means, projections) of every single edit of a few sequences, device tensors in the order substitutions, deletions,
+        insertions: the mutants' means minus the sequences' own in units of the standardised y, and z'^T proj [..., K]."""
+        if type(self.kernel) is Conv1dTwoLayerKernel:
+            res = [self.kernel.edit_scan(input_x, sequence_lengths, self.weights, name, proj=proj)
+                   for name in ("substitutions", "deletions", "insertions")]
+            return [r[0] for r in res], [r[1] for r in res]
+        means = (self.kernel.substitution_scan(input_x, sequence_lengths, self.weights),) \
+            + tuple(self.kernel.indel_scan(input_x, sequence_lengths, self.weights))
+        projs = (self.kernel.substitution_projection_scan(input_x, sequence_lengths, proj),) \
+            + tuple(self.kernel.indel_projection_scan(input_x, sequence_lengths, proj))
+        return list(means), list(projs)
+
+    def single_edit_neighbourhoods(self, input_x, sequence_lengths=None, token_table=None):
+        """Iterator of ``acquisition.SingleEditPosterior``, one per sequence (no counterpart in the reference): the JOINT posterior
+        of every single substitution, deletion and insertion of that sequence -- means in the units of y, and a factor [E, nvar]
+        of the latent posterior covariance, trainy_std^2 lambda^2 z'^T var z'', whose squared row norms plus ``noise`` are the
+        variances of ``predict_single_edits(get_var=True)``.  The factor is the mutants' variance columns times a square-root
+        factor of ``var`` (``torch.linalg.eigh``, cached), from the projection scans: the window sums of the variance scans and
+        one matrix-core product per slab, no mutant written (``ConvSORFKernel.substitution_projection_scan``; Conv1dTwoLayer:
+        ``edit_scan(proj=...)``).  One sequence at a time: E nvar 8 bytes are held.  Input, kernels and refusals as for
+        ``predict_single_edits(get_var=True)``."""
+        from .acquisition import SingleEditPosterior
+        input_x, sequence_lengths = self._joint_scan_input("single_edit_neighbourhoods", input_x, sequence_lengths, token_table)
+        L, V = input_x.shape[1], input_x.table.shape[0]
+        amp = self.trainy_std * float(self.kernel.get_lambda())
+        factor = self._factor_of_var()
+
+        def neighbourhoods():
+            for i in range(input_x.shape[0]):
+                xb, lens = input_x[i:i + 1], sequence_lengths[i:i + 1]
+                s = int(lens[0])
+                own = float(self.predict(xb, lens)[0])
+                means, projs = self._edit_projections(xb, lens, factor)
+                mean = torch.cat([m.reshape(-1) for m in means]) * self.trainy_std + own
+                fac = torch.cat([p.reshape(-1, factor.shape[1]) for p in projs]) * amp
+                pos = torch.arange(L + 1, device=mean.device)
+                toks = torch.arange(V, device=mean.device)
+                sub = (pos[:L, None] < s) & (toks[None, :] != xb.tokens[0].long()[:, None])
+                dele = (pos[:L] < s) & (s > self.kernel.conv_width)
+                ins = (pos[:, None] <= s).expand(L + 1, V)
+                valid = torch.cat([sub.reshape(-1), dele, ins.reshape(-1)])
+                past = torch.cat([(pos[:L, None] >= s).expand(L, V).reshape(-1), pos[:L] >= s, ~ins.reshape(-1)])
+                yield SingleEditPosterior(mean.masked_fill_(past, 0.0), fac, amp ** 2, valid, L, V)
+        return neighbourhoods()
+
+    def sample_single_edits(self, input_x, sequence_lengths=None, token_table=None, n_samples=16, random_seed=123, chunk_size=16):
+        """Joint posterior draws of EVERY single edit (Thompson sampling; no counterpart in the reference) -> the dict of
+        ``predict_single_edits`` with a trailing axis of ``n_samples``: "substitutions" [N, L, V, S], "deletions" [N, L, S] and
+        "insertions" [N, L + 1, V, S], numpy float64.  Entry [..., k] is the k-th draw of the mutant's latent value in the units
+        of y, mean + trainy_std lambda z'^T F eps_k with F F^T = var and ONE eps_k ~ N(0, I) (``acquisition.standard_normal(nvar,
+        n_samples, random_seed)``) for every edit of every sequence, so the draws carry the covariance between mutants: column k
+        is what ``SingleEditPosterior.sample`` gives.  Exactly 0 past a sequence's length, NaN for the deletions of a sequence of
+        conv_width tokens, the sequence's own draw at its own token.  One projection scan with K = n_samples columns,
+        ``proj = F @ eps``: no neighbourhood object and no [E, nvar] factor is formed.  Input, kernels and refusals as for
+        ``predict_single_edits(get_var=True)``; ``chunk_size`` sequences go to the device at a time."""
+        from .acquisition import standard_normal
+        input_x, sequence_lengths = self._joint_scan_input("sample_single_edits", input_x, sequence_lengths, token_table)
+        n, L, V = input_x.shape[0], input_x.shape[1], input_x.table.shape[0]
+        factor = self._factor_of_var()
+        proj = factor @ standard_normal(factor.shape[1], n_samples, random_seed).to(factor.device)
+        amp = self.trainy_std * float(self.kernel.get_lambda())
+        names = ("substitutions", "deletions", "insertions")
+        out = {nm: np.zeros(shape + (n_samples,)) for nm, shape in zip(names, ((n, L, V), (n, L), (n, L + 1, V)))}
+        for i in range(0, n, chunk_size):
+            xb, lens = input_x[i:i + chunk_size], sequence_lengths[i:i + chunk_size]
+            own = torch.from_numpy(np.asarray(self.predict(xb, lens), dtype=np.float64)).to(proj.device)
+            means, projs = self._edit_projections(xb, lens, proj)
+            for nm, m, p in zip(names, means, projs):
+                draws = (m * self.trainy_std + own.view((-1,) + (1,) * (m.dim() - 1)))[..., None] + amp * p
+                site = np.arange(m.shape[1])[None, :]
+                draws = draws.cpu().numpy()
+                draws[site > lens[:, None] if nm == "insertions" else site >= lens[:, None]] = 0
+                out[nm][i:i + chunk_size] = draws
+        return out
+
+    def select_single_edit_batch(self, input_x, sequence_lengths=None, token_table=None, batch_size=8, beta=2.0, maximize=True):
+        """A plate of ``batch_size`` single-edit mutants per sequence that are informative TOGETHER (no counterpart in the reference)
+        -> one list per sequence, as ``SingleEditPosterior.select_batch`` returns it: dicts (index, kind, position, token, mean,
+        sd) in the order picked.  Greedy GP-BUCB on the joint posterior of ``single_edit_neighbourhoods``: each pick maximises
+        mean + beta sd (``maximize`` False: minimises mean - beta sd) with sd conditioned on the earlier picks, so the same
+        position with three similar residues is not picked three times as a top-B of marginal UCBs would."""
+        return [nb.select_batch(batch_size, beta=beta, maximize=maximize)
+                for nb in self.single_edit_neighbourhoods(input_x, sequence_lengths, token_table)]
+
     def predict_window_scores(self, input_x, sequence_lengths=None, token_table=None, chunk_size=64):
         """The share of every k-mer window in ``predict`` (no counterpart in the reference) -> numpy float64 [N, L]: entry
         [i, j] is what window j = tokens j .. j + conv_width - 1 of sequence i adds to the predicted mean, in the units of y;

@@ -1263,6 +1263,82 @@ def hipConvTokenIndelVarScan(tokens, table, vm, u_del, q_del, u_ins, q_ins, dele
         int(scaling_type), int(bool(fit_intercept)), int(slab_rows), wp, wn, _stream()))
 
 
+def conv_token_edit_proj_ok(width, vocab, C, num_freqs, nvar, K):
+    """Whether the kernels of hipConvTokenSubstProj / hipConvTokenIndelProj serve the shape: where
+    ``conv_token_subst_var_scan_ok`` is 1 and 1 <= K <= 2048; no device work."""
+    return int(_LIB.xgpr_conv_token_edit_proj_ok(int(width), int(vocab), int(C), int(num_freqs), int(nvar), int(K)))
+
+
+def conv_token_edit_proj_workspace_bytes(radem_shape2, nvar, slab_rows=0):
+    """The exact workspace of hipConvTokenSubstProj / hipConvTokenIndelProj in bytes -- that of the variance scans: the packed sign
+    masks and ``slab_rows`` float64 rows of ``nvar`` columns (0: the library's default)."""
+    return int(_LIB.xgpr_conv_token_edit_proj_workspace_bytes(int(radem_shape2), int(nvar), int(slab_rows)))
+
+
+def _proj_matrix(pm):
+    """``pm`` of hipConvTokenSubstProj and hipConvTokenIndelProj, checked: -> (nvar, K)."""
+    if pm.dim() != 2 or pm.dtype != torch.float64 or not pm.is_cuda or pm.stride(1) != 1 or pm.shape[1] < 1:
+        raise RuntimeError("pm must be a float64 device matrix [nvar, K] with contiguous rows.")
+    return pm.shape[0], pm.shape[1]
+
+
+def hipConvTokenSubstProj(tokens, table, pm, b, out, radem, chi, seqlen, conv_width, scaling_type, fit_intercept, slab_rows=0,
+                          workspace=None):
+    """``out[n, L, V, K]`` (float64, OVERWRITTEN) <- ``z'^T pm`` over the first ``nvar = pm.shape[0]`` feature columns z' of the
+    sequence with token l replaced by v, for every position l and token v of the sequence and graph kernels
+    (include/xgpr_hip/edit_proj.h): ``b[i]`` bit for bit at a sequence's own token, exactly 0.0 past its length.  ``pm`` float64
+    [nvar, K] (rows may be strided; nvar even), ``b`` [n, K] = the sequences' columns times pm, float64 and precomputed by the
+    caller.  ``slab_rows`` as for hipConvTokenSubstVarScan.  Shapes for which ``conv_token_edit_proj_ok`` is 0 raise RuntimeError
+    and launch nothing."""
+    t, tab = _dev(tokens, "tokens", torch.uint8, 2), _dev(table, "table", torch.float32, 2)
+    r, c = _radem3(radem), _dev(chi, "chi", torch.float32, 1)
+    g = _dev(out, "out", torch.float64, 4)
+    n, L = tokens.shape
+    nvar, K = _proj_matrix(pm)
+    bb = _dev(b, "b", torch.float64, 2)
+    if tuple(out.shape) != (n, L, table.shape[0], K) or tuple(b.shape) != (n, K):
+        raise RuntimeError("Wrong array sizes.")
+    host, dev, slab_rows, ws, wp, wn = _var_scan_workspace(tokens, radem, seqlen, nvar, n * L * table.shape[0], slab_rows, workspace,
+                                                           conv_token_edit_proj_workspace_bytes)
+    return _lib.check(_LIB.xgpr_conv_token_subst_proj_f32(
+        t, tab, C.c_void_p(pm.data_ptr()), pm.stride(0), bb, g, r, c, C.c_void_p(host.ctypes.data), C.c_void_p(dev.data_ptr()), n, L,
+        table.shape[0], table.shape[1], chi.shape[0], radem.shape[2], nvar, K, int(conv_width), int(scaling_type),
+        int(bool(fit_intercept)), int(slab_rows), wp, wn, _stream()))
+
+
+def hipConvTokenIndelProj(tokens, table, pm, b_del, b_ins, deletions, insertions, radem, chi, seqlen, conv_width, scaling_type,
+                          fit_intercept, slab_rows=0, workspace=None):
+    """``deletions[n, L, K]`` <- ``z'^T pm`` over the first ``nvar = pm.shape[0]`` feature columns z' of the sequence without its
+    token at p, and ``insertions[n, L + 1, V, K]`` <- the same for the sequence with table row v inserted before position g (g =
+    length appends); both float64 and OVERWRITTEN, exactly 0.0 past a sequence's length, quiet NaN for the deletions of a
+    sequence of conv_width tokens (include/xgpr_hip/edit_proj.h).  ``b_del``, ``b_ins`` [n, K] = b^T pm for the sequences'
+    rescaled columns b = rho z + (1 - rho) e0 with each row set's own rho, float64 and precomputed by the caller.  Either group
+    (b, output) may be None as a whole (that half is skipped), not both.  ``slab_rows`` as for hipConvTokenIndelVarScan.  Shapes
+    for which ``conv_token_edit_proj_ok`` is 0 raise RuntimeError and launch nothing."""
+    t, tab = _dev(tokens, "tokens", torch.uint8, 2), _dev(table, "table", torch.float32, 2)
+    r, c = _radem3(radem), _dev(chi, "chi", torch.float32, 1)
+    n, L = tokens.shape
+    V = table.shape[0]
+    nvar, K = _proj_matrix(pm)
+    ptrs = []
+    for b, out, shape, what in ((b_del, deletions, (n, L, K), "deletions"), (b_ins, insertions, (n, L + 1, V, K), "insertions")):
+        if b is None and out is None:
+            ptrs.append((None, None))
+            continue
+        if b is None or out is None:
+            raise RuntimeError(f"{what}: b and the output are given together or not at all.")
+        ptrs.append((_dev(b, "b", torch.float64, 2), _dev(out, what, torch.float64, len(shape))))
+        if tuple(out.shape) != shape or tuple(b.shape) != (n, K):
+            raise RuntimeError("Wrong array sizes.")
+    host, dev, slab_rows, ws, wp, wn = _var_scan_workspace(tokens, radem, seqlen, nvar, n * (L + 1) * V, slab_rows, workspace,
+                                                           conv_token_edit_proj_workspace_bytes)
+    (bd, od), (bi, oi) = ptrs
+    return _lib.check(_LIB.xgpr_conv_token_indel_proj_f32(
+        t, tab, C.c_void_p(pm.data_ptr()), pm.stride(0), bd, bi, od, oi, r, c, C.c_void_p(host.ctypes.data),
+        C.c_void_p(dev.data_ptr()), n, L, V, table.shape[1], chi.shape[0], radem.shape[2], nvar, K, int(conv_width),
+        int(scaling_type), int(bool(fit_intercept)), int(slab_rows), wp, wn, _stream()))
+
+
 def conv_maxpool_input_grad_ok(width):
     """Whether hipConvMaxpoolInputGrad's kernel serves a window of ``width`` = conv_width * C elements (padded width up to 1024)."""
     return int(_LIB.xgpr_conv_maxpool_input_grad_ok(int(width)))
