@@ -173,6 +173,14 @@ EDIT_PROJ_ABI = {
     "xgpr_conv_token_indel_proj_f32": [_vp, _vp, _vp, _l, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _l, _l, _l, _l, _l, _l, _l, _l, _i, _i,
                                        _i, _l, _vp, _sz, _vp],
 }
+# ... and include/xgpr_hip/site_scan.h, the fourteenth (tests/test_site_scan_host.py); named like the twelfth's table, for its reason; its
+# *_workspace_bytes function returns size_t and its *_layout function long
+SITE_SCAN_ABI = {
+    "xgpr_conv_token_site_scan_ok": [_l, _l, _l, _l, _i],
+    "xgpr_conv_token_site_scan_layout": [_vp, _i, _l, _i, _l, _vp, _vp, _vp, _vp, _vp, _i],
+    "xgpr_conv_token_site_scan_workspace_bytes": [_l, _l, _i],
+    "xgpr_conv_token_site_scan_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _l, _l, _l, _l, _l, _l, _i, _i, _i, _vp, _sz, _vp],
+}
 STRING_FUNCS = ["xgpr_last_error", "xgpr_build_arch", "xgpr_build_id"]
 
 _lib = None
@@ -195,12 +203,14 @@ def load():
                        + list(SEQ_INPUT_GRAD_SIGNATURES.items()) + list(POOL_INPUT_GRAD_SIGNATURES.items()) + list(CLUSTER_SIGNATURES.items())
                        + list(SUBST_SCAN_SIGNATURES.items()) + list(INDEL_SCAN_SIGNATURES.items())
                        + list(SUBST_VAR_SCAN_SIGNATURES.items()) + list(INDEL_VAR_SCAN_SIGNATURES.items())
-                       + list(PAIR_SCAN_SIGNATURES.items()) + list(POOL_EDITS_ABI.items()) + list(EDIT_PROJ_ABI.items())):
+                       + list(PAIR_SCAN_SIGNATURES.items()) + list(POOL_EDITS_ABI.items()) + list(EDIT_PROJ_ABI.items())
+                       + list(SITE_SCAN_ABI.items())):
         fn = getattr(lib, name)
         fn.argtypes = args
         sized = (name in CLUSTER_SIGNATURES or name in SUBST_VAR_SCAN_SIGNATURES or name in INDEL_VAR_SCAN_SIGNATURES
-                 or name in EDIT_PROJ_ABI)
-        fn.restype = C.c_size_t if sized and name.endswith("_workspace_bytes") else C.c_int
+                 or name in EDIT_PROJ_ABI or name in SITE_SCAN_ABI)
+        fn.restype = (C.c_size_t if sized and name.endswith("_workspace_bytes")
+                      else C.c_long if name == "xgpr_conv_token_site_scan_layout" else C.c_int)
     for name, args in SIZE_FUNCS.items():
         fn = getattr(lib, name)
         fn.argtypes = args

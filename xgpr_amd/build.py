@@ -27,6 +27,7 @@ INDEL_VAR_SCAN_HDR = os.path.join(HERE, "..", "include", "xgpr_hip_indel_var_sca
 PAIR_SCAN_HDR = os.path.join(HERE, "..", "include", "xgpr_hip_pair_scan.h")      # the eleventh
 POOL_EDITS_HDR = os.path.join(HERE, "..", "include", "xgpr_hip", "pool_edits.h")      # the twelfth (in a subdirectory: see its own comment)
 EDIT_PROJ_HDR = os.path.join(HERE, "..", "include", "xgpr_hip", "edit_proj.h")      # the thirteenth (next to the twelfth)
+SITE_SCAN_HDR = os.path.join(HERE, "..", "include", "xgpr_hip", "site_scan.h")      # the fourteenth (next to the twelfth)
 LIB = os.path.join(HERE, "libxgpr_hip.so")
 # Roofline probe, NOT a product library: the same translation unit with -DXGPR_ABL_VALUONLY, in which the fused CG
 # matvec keeps its vector instruction stream but has its LDS traffic, workgroup barrier and prefetch DMA compiled
@@ -50,13 +51,13 @@ def hipcc_path():
 def sources():
     """xgpr_hip.hip is one translation unit that includes the .inc files next to it."""
     csrc = os.path.dirname(SRC)
-    return [SRC, HDR, POOL_HDR, INPUT_GRAD_HDR, SEQ_INPUT_GRAD_HDR, POOL_INPUT_GRAD_HDR, CLUSTER_HDR, SUBST_SCAN_HDR, INDEL_SCAN_HDR, SUBST_VAR_SCAN_HDR, INDEL_VAR_SCAN_HDR, PAIR_SCAN_HDR, POOL_EDITS_HDR, EDIT_PROJ_HDR] + sorted(os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".inc"))
+    return [SRC, HDR, POOL_HDR, INPUT_GRAD_HDR, SEQ_INPUT_GRAD_HDR, POOL_INPUT_GRAD_HDR, CLUSTER_HDR, SUBST_SCAN_HDR, INDEL_SCAN_HDR, SUBST_VAR_SCAN_HDR, INDEL_VAR_SCAN_HDR, PAIR_SCAN_HDR, POOL_EDITS_HDR, EDIT_PROJ_HDR, SITE_SCAN_HDR] + sorted(os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".inc"))
 
 
 def source_id(extra_flags=()):
     """sha256 over what determines the binary: every file of the translation unit (csrc/*, include/xgpr_hip.h, include/xgpr_hip_pool.h, include/xgpr_hip_input_grad.h,
     include/xgpr_hip_seq_input_grad.h, include/xgpr_hip_pool_input_grad.h, include/xgpr_hip_cluster.h, include/xgpr_hip_subst_scan.h,
-    include/xgpr_hip_indel_scan.h, include/xgpr_hip_subst_var_scan.h, include/xgpr_hip_indel_var_scan.h, include/xgpr_hip_pair_scan.h, include/xgpr_hip/pool_edits.h, include/xgpr_hip/edit_proj.h: name and
+    include/xgpr_hip_indel_scan.h, include/xgpr_hip_subst_var_scan.h, include/xgpr_hip_indel_var_scan.h, include/xgpr_hip_pair_scan.h, include/xgpr_hip/pool_edits.h, include/xgpr_hip/edit_proj.h, include/xgpr_hip/site_scan.h: name and
     contents, in sorted order) and the flag list.  Baked into the library at compile time (-DXGPR_BUILD_ID) and
     returned by xgpr_build_id(): a .so states which tree it was built from, and build() rebuilds on a mismatch --
     modification times are not consulted (a checkout of older sources leaves the .so NEWER than them)."""

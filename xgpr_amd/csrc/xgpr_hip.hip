@@ -57,6 +57,7 @@ typedef enum { ncclFloat64 = 8 } ncclDataType_t;
 #include "../../include/xgpr_hip_pair_scan.h"
 #include "../../include/xgpr_hip/pool_edits.h"
 #include "../../include/xgpr_hip/edit_proj.h"
+#include "../../include/xgpr_hip/site_scan.h"
 
 namespace {
 
@@ -79,6 +80,7 @@ namespace {
 #include "seq_input_grad.inc"
 #include "edit_scan.inc"
 #include "pair_scan.inc"
+#include "site_scan.inc"
 #include "var_scan.inc"
 #include "edit_proj.inc"
 #include "pool_input_grad.inc"
@@ -713,6 +715,27 @@ int xgpr_conv_token_indel_proj_f32(const uint8_t *tokens, const float *table, co
     return indel_proj_impl(tokens, table, pm, pm_stride, b_del, b_ins, out_del, out_ins, radem, chi, seqlen_host, seqlen_dev, n, L, vocab,
                            C, num_freqs, radem_shape2, nvar, K, conv_width, scaling_type, fit_intercept, slab_rows, workspace,
                            workspace_bytes, stream);
+}
+
+// ---- include/xgpr_hip/site_scan.h
+int xgpr_conv_token_site_scan_ok(long width, long vocab, long C, long num_freqs, int max_cover) {
+    return conv_token_site_scan_ok_impl(width, vocab, C, num_freqs, max_cover);
+}
+long xgpr_conv_token_site_scan_layout(const int32_t *sites_host, int K, long L, int conv_width, long vocab, int32_t *run_first_window,
+                                      int32_t *run_last_window, int32_t *run_first_site, int32_t *run_sites, int64_t *run_offset,
+                                      int max_runs) {
+    return site_scan_layout_impl(sites_host, K, L, conv_width, vocab, run_first_window, run_last_window, run_first_site, run_sites,
+                                 run_offset, max_runs);
+}
+size_t xgpr_conv_token_site_scan_workspace_bytes(long radem_shape2, long n, int K) {
+    return site_scan_workspace_bytes_impl(radem_shape2, n, K);
+}
+int xgpr_conv_token_site_scan_f32(const uint8_t *tokens, const float *table, const double *w, double *out, const int8_t *radem,
+                                  const float *chi, const int32_t *seqlen_host, const int32_t *seqlen_dev, const int32_t *sites_host,
+                                  int K, long n, long L, long vocab, long C, long num_freqs, long radem_shape2, int conv_width,
+                                  int scaling_type, int fit_intercept, void *workspace, size_t workspace_bytes, void *stream) {
+    return site_scan_impl(tokens, table, w, out, radem, chi, seqlen_host, seqlen_dev, sites_host, K, n, L, vocab, C, num_freqs,
+                          radem_shape2, conv_width, scaling_type, fit_intercept, workspace, workspace_bytes, stream);
 }
 
 int xgpr_selftest_lane_xor(int32_t *out, void *stream) {

@@ -704,6 +704,94 @@ class ConvSORFKernel(KernelBase):
         out.masked_fill_((tok[None, None, :] == own[:, :, None])[:, :, None, :, None], 0.0)
         return out.masked_fill_((tok[None, None, None, :] == own[:, second.clamp(max=L - 1)][:, :, :, None])[:, :, :, None, :], 0.0)
 
+    # ---- every variant of K chosen sites, as a sum of one small table per set of sites a window sees together
+    SITE_SCAN_ROWS = 1 << 24         # grid rows one launch serves (xgpr_conv_token_site_scan_f32: one workgroup each)
+    SITE_SCAN_VARIANTS = 1 << 22     # V^K the composed route writes out per sequence, at the most
+
+    def _site_list(self, sites, L, lengths):
+        s = np.asarray(sites)
+        if s.ndim != 1 or s.shape[0] < 1 or s.dtype.kind not in "iu":
+            raise RuntimeError("sites must be a non-empty list of integer positions.")
+        s = s.astype(np.int64)
+        if (np.diff(s) <= 0).any() or int(s[0]) < 0 or int(s[-1]) >= L:
+            raise RuntimeError("sites must be strictly ascending positions inside the array.")
+        if lengths.shape[0] and int(s[-1]) >= int(lengths.min()):
+            raise RuntimeError("every site must lie inside every sequence of the batch.")
+        return [int(p) for p in s]
+
+    def site_scan(self, batch, sequence_length, weights, sites):
+        """``SiteLibrary`` of the K positions ``sites`` (strictly ascending, shared by the batch and inside every sequence): every
+        one of the V^K variants of every sequence, as ``transform_x(variant) @ weights`` minus ``transform_x(sequence) @ weights``,
+        held as one table per RUN -- a set of sites that one range of windows covers together -- of V^g entries, g the sites of
+        the run.  A variant's value is the sum of one entry per run, exactly, for ANY number of sites inside a window (the
+        singles-plus-pairs recipe of ``pair_substitution_scan`` is exact for two).  Only the windows that cover a site are
+        transformed, each for the assignments of the sites it covers, and no variant is written (``ext.hipConvTokenSiteScan``);
+        the entry of a sequence's own tokens is exactly 0 in every table.  A batch of more than ``SITE_SCAN_ROWS`` grid rows
+        goes to the operator in slices.  Where ``ext.conv_token_site_scan_ok`` is 0 (windows of more than 1024 elements, a table
+        the LDS image does not hold, more than 4 sites inside one window), with more than 16 sites or where the tokens are not
+        contiguous the result comes from ``site_scan_composed``."""
+        from .acquisition import SiteLibrary, site_runs
+        xs, lengths, w = self._scan_inputs(batch, sequence_length, weights)
+        n, L, _ = xs.shape
+        V = xs.table.shape[0]
+        sites = self._site_list(sites, L, lengths)
+        runs = site_runs(sites, L, self.conv_width)
+        cover = max(g for _, _, _, g in runs)
+        rows = sum(V ** (g - 1) for _, _, _, g in runs) if cover <= 4 else self.SITE_SCAN_ROWS
+        if (len(sites) > 16 or rows >= self.SITE_SCAN_ROWS
+                or not self._scan_operator_ok(xs, lambda *a: ext.conv_token_site_scan_ok(*a, cover))):
+            return self._site_scan_composed(xs, lengths, w, sites)
+        layout, T = ext.conv_token_site_scan_layout(sites, L, self.conv_width, V)
+        out = torch.empty((n, T), dtype=torch.float64, device=self.device)
+        table = xs.table.contiguous()
+        step = max(1, (self.SITE_SCAN_ROWS - 1) // rows)
+        for lo in range(0, max(n, 1), step):             # (n == 0: one call, for its checks)
+            ext.hipConvTokenSiteScan(xs.tokens[lo:lo + step], table, w, out[lo:lo + step], self.radem_diag, self.chi_arr,
+                                     lengths[lo:lo + step], sites, self.conv_width, self.scaling_type, self.fit_intercept)
+        tables = [out[:, r["offset"]:r["offset"] + V ** r["sites"]].reshape((n,) + (V,) * r["sites"]) for r in layout]
+        return SiteLibrary(sites, V, [range(r["first_site"], r["first_site"] + r["sites"]) for r in layout], tables)
+
+    def site_scan_composed(self, batch, sequence_length, weights, sites):
+        """The same library from existing operators, at every window width and table size, as ONE run over all K sites: bounded
+        slices of written-out variants go through ``fill_feature_rows`` and ``hipZCacheBlockProject`` with one column, and an
+        entry is m(variant) - m(sequence); the own assignment is set to an exact zero.  At most ``COMPOSED_SCAN_ELEMS`` float32
+        row elements are held at a time; more than ``SITE_SCAN_VARIANTS`` = 2^22 variants per sequence are refused."""
+        xs, lengths, w = self._scan_inputs(batch, sequence_length, weights)
+        return self._site_scan_composed(xs, lengths, w, self._site_list(sites, xs.shape[1], lengths))
+
+    def _site_scan_composed(self, xs, lengths, w, sites):
+        from .acquisition import SiteLibrary
+        n, L, _ = xs.shape
+        V, K, dev = xs.table.shape[0], len(sites), self.device
+        self._check_lengths(lengths, n, L)
+        if V ** K > self.SITE_SCAN_VARIANTS:
+            raise RuntimeError(f"site_scan_composed would write out {V}^{K} variants per sequence, more than SITE_SCAN_VARIANTS = "
+                               f"{self.SITE_SCAN_VARIANTS}: the composed route serves small libraries only (the operator route "
+                               "needs windows of up to 1024 elements and at most 4 sites inside one window).")
+        nv = V ** K
+        project = self._projector(xs.table, w)
+        tokens = xs.tokens.contiguous()
+        step = max(1, self.COMPOSED_SCAN_ELEMS // self.num_rffs)
+        base = torch.empty(n, dtype=torch.float64, device=dev)
+        for lo in range(0, n, step):
+            base[lo:lo + step] = project(tokens[lo:lo + step], lengths[lo:lo + step])
+        out = torch.empty((n, nv), dtype=torch.float64, device=dev)
+        flat = out.view(-1)
+        own = torch.zeros(n, dtype=torch.long, device=dev)
+        for p in sites:
+            own = own * V + tokens[:, p].long()
+        for lo in range(0, n * nv, step):
+            ids = torch.arange(lo, min(lo + step, n * nv), device=dev)
+            seq, var = ids // nv, ids % nv
+            mut = tokens[seq]
+            rows = torch.arange(ids.shape[0], device=dev)
+            for k, p in enumerate(sites):
+                mut[rows, p] = ((var // V ** (K - 1 - k)) % V).to(torch.uint8)
+            flat[lo:lo + step] = project(mut, lengths[seq.cpu().numpy()]) - base[seq]
+        if n:
+            out[torch.arange(n, device=dev), own] = 0.0  # the own assignment: the variant is the sequence itself
+        return SiteLibrary(sites, V, [range(K)], [out.reshape((n,) + (V,) * K)])
+
     # ---- the exact quadratic form of the predictive variance of every single-token substitution (DESIGN.md 3.22)
     def _var_scan_inputs(self, batch, sequence_length, var):
         if not isinstance(batch, TokenBatch):

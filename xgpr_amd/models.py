@@ -319,6 +319,30 @@ class xGPRegression(_ModelBase):
             out[i:i + chunk_size] = scan.cpu().numpy() * self.trainy_std
         return out
 
+    def predict_site_library(self, input_x, sites, sequence_lengths=None, token_table=None, chunk_size=4):
+        """Every variant of the K positions ``sites`` of every sequence -- a combinatorial site-saturation library, V^K variants
+        per parent -- as a ``SiteLibrary`` (no counterpart in the reference): one small table per RUN, a set of sites that one
+        range of k-mer windows covers together, in the units of y (times the training y's standard deviation), and ``base`` =
+        ``predict`` of the parents, so that
+
+            mean(variant) = lib.base[:, None] + lib.gather(assignments)
+
+        exactly, for ANY number of chosen sites inside one window -- where ``predict_substitutions`` plus
+        ``predict_substitution_pairs`` is exact for two.  ``lib.topk(k)`` gives the k best variants of each parent without
+        forming V^K; ``lib.dense()`` the whole library where it is small enough.  ``sites`` are strictly ascending positions
+        shared by all sequences and inside every one of them (a per-sequence site list: one call per sequence).  The entry
+        of a parent's own tokens is exactly 0 in every table.  Input, kernels and refusals as for ``predict_substitutions``.
+        Only the windows that cover a site are transformed, each for the assignments of the sites it covers, and no variant is
+        written (``ConvSORFKernel.site_scan``, which names the shapes that are written out instead).  The
+        tables are CPU tensors; ``chunk_size`` sequences go to the device at a time."""
+        from .acquisition import SiteLibrary
+        input_x, sequence_lengths = self._token_scan_input("predict_site_library", input_x, sequence_lengths, token_table)
+        libs = [self.kernel.site_scan(input_x[i:i + chunk_size], sequence_lengths[i:i + chunk_size], self.weights, sites)
+                for i in range(0, max(input_x.shape[0], 1), chunk_size)]
+        tables = [torch.cat([lib.tables[q] for lib in libs]).cpu() * float(self.trainy_std) for q in range(len(libs[0].tables))]
+        base = torch.from_numpy(np.asarray(self.predict(input_x, sequence_lengths=sequence_lengths), dtype=np.float64).reshape(-1))
+        return SiteLibrary(libs[0].sites, libs[0].vocab, libs[0].runs, tables, base=base)
+
     def predict_indels(self, input_x, sequence_lengths=None, token_table=None, chunk_size=64, get_var=False):
         """The exact effect of every single deletion and insertion on ``predict`` (no counterpart in the reference) -> numpy
         float64 (deletions [N, L], insertions [N, L + 1, V]): deletions[i, p] is the predicted mean of sequence i without its

@@ -1110,6 +1110,73 @@ def hipConvTokenPairScan(tokens, table, weights, out, radem, chi, seqlen, conv_w
         chi.shape[0], radem.shape[2], int(conv_width), int(scaling_type), int(bool(fit_intercept)), wp, wn, _stream()))
 
 
+def conv_token_site_scan_ok(width, vocab, C, num_freqs, max_cover):
+    """Whether hipConvTokenSiteScan's kernels serve a window of ``width`` = conv_width * C elements over a table of ``vocab`` rows
+    and ``C`` columns (where ``conv_token_subst_scan_ok`` is 1) with at most ``max_cover`` (1 .. 4) sites inside one window; no
+    device work."""
+    return int(_LIB.xgpr_conv_token_site_scan_ok(int(width), int(vocab), int(C), int(num_freqs), int(max_cover)))
+
+
+def _site_list(sites):
+    s = np.asarray(sites)
+    if s.ndim != 1 or s.dtype.kind not in "iu":
+        raise TypeError("sites: expected a 1-d sequence of integer positions")
+    return np.ascontiguousarray(s.astype(np.int32))
+
+
+def conv_token_site_scan_layout(sites, L, conv_width, vocab):
+    """The runs of a site list on the host (include/xgpr_hip/site_scan.h) -> (runs, T): ``runs`` a list of dicts ``first_window``,
+    ``last_window``, ``first_site`` (an index into ``sites``), ``sites`` (their number g) and ``offset`` into a row of
+    hipConvTokenSiteScan's output, in ascending window order; ``T`` the length of such a row, the sum of vocab^g.  A site list the
+    library refuses (empty, more than 16 sites, not strictly ascending, a site outside 0 .. L - 1) raises RuntimeError."""
+    s = _site_list(sites)
+    K = s.shape[0]
+    cap = max(2 * K - 1, 1)
+    i32 = [np.zeros(cap, dtype=np.int32) for _ in range(4)]
+    off = np.zeros(cap, dtype=np.int64)
+    nr = int(_LIB.xgpr_conv_token_site_scan_layout(C.c_void_p(s.ctypes.data), K, int(L), int(conv_width), int(vocab),
+                                                   *[C.c_void_p(a.ctypes.data) for a in i32], C.c_void_p(off.ctypes.data), cap))
+    if nr < 0:
+        _lib.check(nr)
+    runs = [dict(first_window=int(i32[0][q]), last_window=int(i32[1][q]), first_site=int(i32[2][q]), sites=int(i32[3][q]),
+                 offset=int(off[q])) for q in range(nr)]
+    return runs, (runs[-1]["offset"] + int(vocab) ** runs[-1]["sites"] if runs else 0)
+
+
+def hipConvTokenSiteScan(tokens, table, weights, out, radem, chi, seqlen, sites, conv_width, scaling_type, fit_intercept, workspace=None):
+    """``out[n, T]`` (float64, OVERWRITTEN) <- the run tables of the combinatorial site scan (include/xgpr_hip/site_scan.h): for
+    the runs of ``conv_token_site_scan_layout(sites, L, conv_width, V)``, ``out[i, offset + idx]`` is the summed change of the
+    run's windows under the assignment ``idx`` of the run's sites, and the sum of one entry per run is ``features(sequence with
+    all K sites assigned) @ weights`` minus ``features(sequence) @ weights`` exactly.  Exactly +0.0 at the sequence's own tokens
+    and in a run that has no window inside the sequence.  ``sites``: strictly ascending positions on the host, shared by all
+    sequences and inside every one of them; the other operands as for hipConvTokenSubstScan.  Shapes for which
+    ``conv_token_site_scan_ok`` is 0 -- more than 4 sites inside one window among them -- and batches of 2^24 grid rows or more
+    raise RuntimeError and launch nothing."""
+    ops = (_dev(tokens, "tokens", torch.uint8, 2), _dev(table, "table", torch.float32, 2), _dev(weights, "weights", torch.float64, 1),
+           _radem3(radem), _dev(chi, "chi", torch.float32, 1))
+    g = _dev(out, "out", torch.float64, 2)
+    if weights.shape[0] != 2 * chi.shape[0]:
+        raise RuntimeError("Wrong array sizes.")
+    s = _site_list(sites)
+    n, L = tokens.shape
+    V = table.shape[0]
+    # (a site list or a shape the layout refuses is left to the launcher, which reports it in its documented order)
+    nr = int(_LIB.xgpr_conv_token_site_scan_layout(C.c_void_p(s.ctypes.data), s.shape[0], L, int(conv_width), V, None, None, None, None,
+                                                   None, 0))
+    if nr >= 0 and tuple(out.shape) != (n, conv_token_site_scan_layout(s, L, conv_width, V)[1]):
+        raise RuntimeError("Wrong array sizes.")
+    host, dev = _seqlens(seqlen, tokens.device)
+    if host.shape[0] != n:
+        raise RuntimeError("wrong array sizes")
+    if workspace is None:
+        ws, wp, wn = _workspace(_LIB.xgpr_conv_token_site_scan_workspace_bytes(radem.shape[2], n, s.shape[0]), tokens.device)
+    else:
+        ws, wp, wn = workspace, C.c_void_p(workspace.data_ptr()), C.c_size_t(workspace.numel() * workspace.element_size())
+    return _lib.check(_LIB.xgpr_conv_token_site_scan_f32(
+        *ops[:3], g, *ops[3:], C.c_void_p(host.ctypes.data), C.c_void_p(dev.data_ptr()), C.c_void_p(s.ctypes.data), s.shape[0], n, L, V,
+        table.shape[1], chi.shape[0], radem.shape[2], int(conv_width), int(scaling_type), int(bool(fit_intercept)), wp, wn, _stream()))
+
+
 def _var_scan_nvar(vm):
     """``vm`` of hipConvTokenSubstVarScan and hipConvTokenIndelVarScan, checked: -> nvar."""
     if vm.dim() != 2 or vm.dtype != torch.float64 or not vm.is_cuda or vm.shape[0] != vm.shape[1] or vm.stride(1) != 1:
